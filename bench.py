@@ -8,9 +8,13 @@ N > 1 one RCCL all-reduce(SUM) of grad_d.  The default K = 100 steps are the con
 Every step synthesises and evaluates B adversarial images per GPU, so value = N*B*K / seconds.
 Inputs are synthetic (seeded U[0,1) images, seeded random-init ResNet-50) and resident in HBM before timing.
 
-Extra objects on the JSON line: `roofline` for the dominant hand-written kernel (HIP events recorded on the
-launch stream inside the timed region; algorithmic bytes per launch from DESIGN.md) and `cpu_baseline` (the CPU
-oracle timed on a bounded sample of the same workload on this box's host cores; rank 0, N = 1 only).
+A plain run sets up, warms up, times the steps and prints the headline line, nothing else.  `--full` adds the other
+measurements to the JSON line: `roofline` for the dominant hand-written kernel (HIP events recorded on the launch stream
+inside the timed region; algorithmic bytes per launch from DESIGN.md), per-kernel times, the learn mode's other
+pseudo-label policy timed over as many steps again, and `cpu_baseline` (the CPU oracle timed on a bounded sample of the
+same workload on the host cores; rank 0, N = 1 only).
+
+`--dump-outputs DIR` writes what the timed path computed in its last step as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import json
@@ -64,7 +68,14 @@ def parse_args():
                         "other variant is timed as well and reported in `config`")
     p.add_argument("--fp8-synth", type=int, default=0,
                    help="1: the D.V contraction of the synthesis on fp8 (e4m3) MFMAs (BASELINE.json configs[4]); learn mode")
-    p.add_argument("--cpu-baseline", type=int, default=1)
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: kernel brackets and roofline, the other pseudo-label "
+                        "policy (learn mode), the collective's brackets, the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the timed path computed in its last step as DIR/<name>.npy "
+                        "(learn: d, v, loss, fooled; inference: adversarial_images, codes; transfer: fooling_rate, rmse, mse "
+                        "per target in the order of TRANSFER_TARGETS); at most 60 MB in all, larger arrays as a fixed sample")
+    p.add_argument("--cpu-baseline", type=int, default=1, help="with --full: time the CPU oracle as well")
     p.add_argument("--cpu-batch", type=int, default=48, help="images of the config-2-shape CPU sample (48 images x 1 step per "
                                                              "pseudo-label policy: ~12 + ~18 s on the box's host cores)")
     p.add_argument("--cpu-steps", type=int, default=1)
@@ -121,6 +132,30 @@ class KernelTimer:
             if evs:
                 out[name] = max(sum(a.elapsed_time(b) for a, b in evs) / len(evs) - off, 0.0)
         return out
+
+
+DUMP_BYTES = 60 * 10 ** 6      # --dump-outputs: all arrays together
+
+
+def dump_outputs(path, arrays):
+    """Write every array of `arrays` as path/<name>.npy: float64 stays float64, everything else becomes float32.  The
+    arrays are taken smallest first, and one that is larger than its even share of what DUMP_BYTES has left is written as
+    a flat sample of its elements instead: indices drawn from a generator seeded with 0 and sorted, so that two runs (two
+    builds) at the same arguments sample the same elements."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    items = sorted(((name, torch.as_tensor(a).detach()) for name, a in arrays.items()), key=lambda kv: kv[1].numel())
+    left = DUMP_BYTES
+    for i, (name, a) in enumerate(items):
+        a = a.to(torch.float64 if a.dtype == torch.float64 else torch.float32)
+        share = left // (len(items) - i)
+        if a.numel() * a.element_size() > share:
+            n = share // a.element_size()
+            idx = torch.randint(a.numel(), (n,), generator=torch.Generator().manual_seed(0)).sort().values
+            a = a.reshape(-1)[idx.to(a.device)]
+        a = a.cpu()
+        left -= a.numel() * a.element_size()
+        np.save(os.path.join(path, name + ".npy"), a.numpy())
 
 
 def algorithmic_bytes(B, P, K, N, s, mode="learn"):
@@ -383,20 +418,19 @@ def bench_transfer(args, rank, world, dev, timer):
     if warm is not None:
         perf.get_transfer_performance({"adil": [atk]}, targets, warm, device=dev)
     sync()
-    timer.enabled = True
+    if timer is not None:
+        timer.enabled = True
     t0 = time.perf_counter()
     result = perf.get_transfer_performance({"adil": [atk]}, targets, timed, device=dev)["adil"]
     sync()
     elapsed = time.perf_counter() - t0
-    timer.enabled = False
+    if timer is not None:
+        timer.enabled = False
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {k: torch.tensor([result[n][k] for n in result], dtype=torch.float64)
+                                         for k in ("fooling_rate", "rmse", "mse")})
     if world > 1:
         elapsed = float(adist.all_reduce_(torch.tensor([elapsed], dtype=torch.float64, device=dev), torch.distributed.ReduceOp.MAX))
-    kern_ms = timer.summary_ms()
-    launches = {k: len(v) for k, v in timer.records.items()}
-    alg = algorithmic_bytes(B, P, K, B, s_bytes, "inference")
-    dom = max((k for k in kern_ms if k in alg), key=lambda k: kern_ms[k] * launches[k])
-    achieved = alg[dom] / (kern_ms[dom] * 1e-3) / 1e9
-    iters_run = (launches.get("zstep_", 0) + launches.get("zstep_codes_", 0)) / max(args.steps, 1)
     out = {
         "metric": "attacked images/sec (transfer evaluation: full attack(x, y) + six targets scored, classifiers included)",
         "value": world * B * args.steps / elapsed, "unit": "images/sec",
@@ -409,22 +443,29 @@ def bench_transfer(args, rank, world, dev, timer):
                                 f"image streams, fp32 z + AdamW moments; evaluation set resident in HBM (loader.ResidentBatches)"),
                    "classifier": f"random-init {args.model} (source{', FusedResNet with fp32 logits inside the DDrague loop (head_fp32=inference)' if fused else ''}) and six random-init targets, frozen, eval",
                    "global_batch": world * B, "atoms": K, "steps_inference": args.steps_inference,
-                   "ddrague_iterations_run_per_batch": iters_run,
                    "parallelism": f"dp{world}: batches dealt to ranks (performance.py path), D replicated, final sums all-reduced",
                    "collective": {"backend": torch.distributed.get_backend() if torch.distributed.is_initialized() else None,
                                   "world_size": world, adist.IPC_ENV: os.environ.get(adist.IPC_ENV)},
                    "transfer_fooling_rates": {n: result[n]["fooling_rate"] for n in result},
                    "rmse": next(iter(result.values()))["rmse"]},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic(dom, K),
-                     "mfma_utilisation": measured_mfma_utilisation(dom, K),
-                     "algorithmic_bytes_per_launch": alg[dom], "avg_launch_ms": kern_ms[dom], "launches_timed": launches[dom],
-                     "empty_event_bracket_ms": timer.empty_bracket_ms()},
-        "kernels_ms_per_launch": kern_ms, "kernel_launches_timed": launches,
-        "dictionary_path_ms_per_step": sum(kern_ms[k] * launches[k] for k in kern_ms) / args.steps,
     }
     import shutil
     shutil.rmtree(tmp, ignore_errors=True)                        # the synthetic dictionary file (60 MB at 100 atoms)
+    if not args.full:
+        return out
+    kern_ms = timer.summary_ms()
+    launches = {k: len(v) for k, v in timer.records.items()}
+    alg = algorithmic_bytes(B, P, K, B, s_bytes, "inference")
+    dom = max((k for k in kern_ms if k in alg), key=lambda k: kern_ms[k] * launches[k])
+    achieved = alg[dom] / (kern_ms[dom] * 1e-3) / 1e9
+    out["config"]["ddrague_iterations_run_per_batch"] = (launches.get("zstep_", 0) + launches.get("zstep_codes_", 0)) / max(args.steps, 1)
+    out["roofline"] = {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                       "frac": achieved / HBM_PEAK_GBS, "traffic": measured_traffic(dom, K),
+                       "mfma_utilisation": measured_mfma_utilisation(dom, K),
+                       "algorithmic_bytes_per_launch": alg[dom], "avg_launch_ms": kern_ms[dom], "launches_timed": launches[dom],
+                       "empty_event_bracket_ms": timer.empty_bracket_ms()}
+    out["kernels_ms_per_launch"], out["kernel_launches_timed"] = kern_ms, launches
+    out["dictionary_path_ms_per_step"] = sum(kern_ms[k] * launches[k] for k in kern_ms) / args.steps
     if rank == 0 and world == 1 and args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline_transfer(args, shape)
     return out
@@ -493,7 +534,7 @@ def main():
     torch.cuda.set_device(dev)
 
     from dl_attack_on_imagenet_amd import engine, ops, zoo
-    timer = KernelTimer(ops)
+    timer = KernelTimer(ops) if args.full else None
     if args.mode == "transfer":
         out = bench_transfer(args, rank, world, dev, timer)
         if rank == 0:
@@ -525,7 +566,7 @@ def main():
     v = ops.l1ball_project_(torch.rand(B, K, generator=gen).to(dev), eps)
     # ADIL_FORCE_REDUCER=1 exercises the RCCL path (process group, all-reduce of grad_d) even with one rank
     force = os.environ.get("ADIL_FORCE_REDUCER") == "1" and torch.distributed.is_initialized()
-    reducer = adist.DictGradReducer(timing=True) if (world > 1 or force) else None
+    reducer = adist.DictGradReducer(timing=args.full) if (world > 1 or force) else None
     if args.mode == "inference":
         solver = engine.DDragueSolver(model, x, d, eps, args.loss, False, 50.0)          # Gram / pseudo-inverse: once per call
 
@@ -555,14 +596,21 @@ def main():
     sync()
     if reducer is not None:
         reducer.reset_timing()                                # brackets of the timed steps only
-    timer.enabled = True
+    if timer is not None:
+        timer.enabled = True
     t0 = time.perf_counter()
-    fooled = None
+    loss, fooled = None, None
     for _ in range(args.steps):
-        _, fooled = step()
+        loss, fooled = step()
     sync()
     elapsed = time.perf_counter() - t0
-    timer.enabled = False
+    if timer is not None:
+        timer.enabled = False
+    if args.mode == "inference":
+        adv, codes = solver.result()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, dict(adversarial_images=adv, codes=codes) if args.mode == "inference" else
+                     dict(d=learner.d, v=learner.v, loss=loss, fooled=fooled))
     # what the collective cost: backend, world size, mean start -> wait bracket of the step's all-reduce (HIP events on
     # the compute stream; contains the code-row update that runs underneath); a 1-rank run has no collective
     collective = reducer.describe() if reducer is not None else {
@@ -574,7 +622,7 @@ def main():
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         elapsed = float(adist.all_reduce_(tmax, torch.distributed.ReduceOp.MAX))
     other_variant = None
-    if args.mode == "learn":
+    if args.mode == "learn" and args.full:
         # informational, never `value`: the same steps with the OTHER pseudo-label policy — recomputed in every step (the
         # reference's 2 forwards + 1 backward) when the headline caches them, cached when it recomputes
         fixed = None if args.cache_labels else engine.predict(model, x)
@@ -591,19 +639,9 @@ def main():
                                   if args.cache_labels else "pseudo-labels cached per image, 1 fwd + 1 bwd per step (--cache-labels 1)")}
 
     if args.mode == "inference":
-        adv, _ = solver.result()
         fool_rate = float((engine.predict(model, adv) != solver.labels).float().mean())
     else:
         fool_rate = float(fooled) / B
-    kern_ms = timer.summary_ms()
-    alg = algorithmic_bytes(B, P, K, B, s_bytes, args.mode)
-    dom = max((k for k in kern_ms if k in alg), key=lambda k: kern_ms[k])
-    achieved = alg[dom] / (kern_ms[dom] * 1e-3) / 1e9
-    traffic = measured_traffic(dom, K)                              # from separate rocprofv3 --pmc runs of THIS build, else null
-    # per step, not per launch: a DDrague iteration launches pack_codes twice (the codes of the z-step, the code gradient)
-    launches = {k: len(v) for k, v in timer.records.items()}
-    per_step = {k: launches.get(k, 0) / max(args.steps, 1) for k in kern_ms}
-    dict_ms = sum(kern_ms[k] * per_step[k] for k in kern_ms)
     out = {
         "metric": "adversarial images/sec (ADiL learning step, classifier included)" if args.mode == "learn" else
                   "adversarial images/sec (ADiL DDrague inference iteration, classifier included)",
@@ -633,23 +671,34 @@ def main():
                    "parallelism": f"dp{world}: images+codes sharded, D replicated, 1 all-reduce(grad_d)/step",
                    "collective": collective,
                    ("train_fooling_rate_last_step" if args.mode == "learn" else "fooling_rate_after_timed_iterations"): fool_rate},
-        "roofline": {"bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
-                     "mfma_utilisation": measured_mfma_utilisation(dom, K),     # PMC pass of this build, else null
-                     "algorithmic_bytes_per_launch": alg[dom], "avg_launch_ms": kern_ms[dom],
-                     "empty_event_bracket_ms": timer.empty_bracket_ms(),
-                     # informational: what a cold read + write stream of the synth's image bytes reaches on this pool, whatever its
-                     # access pattern — a flat grid-stride copy included (tools/exp/stream_patterns.hip, profiles/r04_stream_patterns.md)
-                     "measured_copy_ceiling_GBps": 5100.0,
-                     # informational: the same with the cost of an empty event bracket taken off (this is the figure that
-                     # agrees with rocprofv3's kernel duration to ~1 %, profiles/README.md); `achieved`/`frac` stay raw
-                     "frac_minus_empty_bracket": alg[dom] / (max(kern_ms[dom] - timer.empty_bracket_ms(), 1e-6) * 1e-3) / 1e9
-                                                 / HBM_PEAK_GBS},
-        "kernels_ms_per_step": kern_ms,
-        "dictionary_path_ms_per_step": dict_ms,
-        "dictionary_path_algorithmic_GBps": sum(alg[k] * per_step[k] for k in kern_ms if k in alg) / (dict_ms * 1e-3) / 1e9,
-        "kernel_launches_per_step": per_step,
     }
+    if args.full:
+        kern_ms = timer.summary_ms()
+        alg = algorithmic_bytes(B, P, K, B, s_bytes, args.mode)
+        dom = max((k for k in kern_ms if k in alg), key=lambda k: kern_ms[k])
+        achieved = alg[dom] / (kern_ms[dom] * 1e-3) / 1e9
+        traffic = measured_traffic(dom, K)                          # from separate rocprofv3 --pmc runs of THIS build, else null
+        # per step, not per launch: a DDrague iteration launches pack_codes twice (the codes of the z-step, the code gradient)
+        launches = {k: len(v) for k, v in timer.records.items()}
+        per_step = {k: launches.get(k, 0) / max(args.steps, 1) for k in kern_ms}
+        dict_ms = sum(kern_ms[k] * per_step[k] for k in kern_ms)
+        out["roofline"] = {
+            "bound": "hbm", "kernel": dom, "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved / HBM_PEAK_GBS, "traffic": traffic,
+            "mfma_utilisation": measured_mfma_utilisation(dom, K),     # PMC pass of this build, else null
+            "algorithmic_bytes_per_launch": alg[dom], "avg_launch_ms": kern_ms[dom],
+            "empty_event_bracket_ms": timer.empty_bracket_ms(),
+            # informational: what a cold read + write stream of the synth's image bytes reaches on this pool, whatever its
+            # access pattern — a flat grid-stride copy included (tools/exp/stream_patterns.hip, profiles/r04_stream_patterns.md)
+            "measured_copy_ceiling_GBps": 5100.0,
+            # informational: the same with the cost of an empty event bracket taken off (this is the figure that
+            # agrees with rocprofv3's kernel duration to ~1 %, profiles/README.md); `achieved`/`frac` stay raw
+            "frac_minus_empty_bracket": alg[dom] / (max(kern_ms[dom] - timer.empty_bracket_ms(), 1e-6) * 1e-3) / 1e9
+                                        / HBM_PEAK_GBS}
+        out["kernels_ms_per_step"] = kern_ms
+        out["dictionary_path_ms_per_step"] = dict_ms
+        out["dictionary_path_algorithmic_GBps"] = sum(alg[k] * per_step[k] for k in kern_ms if k in alg) / (dict_ms * 1e-3) / 1e9
+        out["kernel_launches_per_step"] = per_step
     if other_variant is not None:
         out["config"]["recomputed_labels_variant" if args.cache_labels else "cached_labels_variant"] = other_variant
         # both pseudo-label policies at the top level as well, so that neither number has to be dug out of `config`:
@@ -667,7 +716,7 @@ def main():
             + "; BENCH_r02.value used the recomputing sequence: compare it with value_reference_op_sequence_recomputed_labels. "
               "The bench replays one resident batch, so the cache always hits — as it does from an image's second epoch on in a "
               "run of the learner (500 epochs in demo_dL_attack.py:92); the first epoch pays the reference's sequence.")
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if rank == 0 and world == 1 and args.full and args.cpu_baseline:
         out["cpu_baseline"] = cpu_baseline(args, shape, dev)
     if rank == 0:
         print(json.dumps(out), flush=True)

@@ -351,6 +351,7 @@ def test_bench_defaults_by_mode_and_traffic_is_tied_to_the_build(tmp_path, monke
     monkeypatch.setattr("sys.argv", ["bench.py"])
     a = bench.parse_args()
     assert (a.mode, a.steps, a.warmup, a.atoms, a.cache_labels, a.gpus) == ("learn", 100, 5, 50, 1, 1)
+    assert a.full is False and a.dump_outputs is None                                   # a plain run: the headline alone
     monkeypatch.setattr("sys.argv", ["bench.py", "--mode", "transfer"])
     a = bench.parse_args()
     assert (a.steps, a.warmup, a.atoms, a.steps_inference) == (4, 1, 100, 100)
@@ -384,6 +385,25 @@ def test_bench_defaults_by_mode_and_traffic_is_tied_to_the_build(tmp_path, monke
             warnings.warn(f"profiles/{name} was measured on another kernel tree: re-run tools/run_profiles.sh pmc / mfma")
     a50 = bench.algorithmic_bytes(512, 150528, 50, 512, 2, "learn")
     assert a50["synth"] == 2 * 512 * 150528 * 2 + 150528 * 50 * 4 + 512 * 50 * 4          # 338.5 MB
+
+
+def test_bench_dump_outputs_is_float_and_bounded(tmp_path, monkeypatch):
+    """bench.py --dump-outputs: every array as <name>.npy in float32 (float64 kept); what does not fit the byte budget is a
+    flat sample of its elements, the same elements in every run."""
+    import numpy as np
+    import bench
+    monkeypatch.setattr(bench, "DUMP_BYTES", 4000)
+    g = torch.Generator().manual_seed(3)
+    arrays = {"big": torch.rand(40, 50, generator=g), "half": torch.rand(6, 7, generator=g).half(),
+              "f64": torch.rand(5, dtype=torch.float64, generator=g), "n": torch.tensor(7)}
+    bench.dump_outputs(str(tmp_path / "a"), arrays)
+    bench.dump_outputs(str(tmp_path / "b"), arrays)
+    got = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in arrays}
+    assert got["f64"].dtype == np.float64 and all(got[k].dtype == np.float32 for k in ("big", "half", "n"))
+    assert np.array_equal(got["f64"], arrays["f64"].numpy()) and float(got["n"]) == 7.0 and got["half"].shape == (6, 7)
+    assert sum(a.nbytes for a in got.values()) <= 4000 and got["big"].ndim == 1 and 0 < got["big"].size < 2000
+    assert np.isin(got["big"], arrays["big"].numpy()).all()
+    assert np.array_equal(got["big"], np.load(tmp_path / "b" / "big.npy"))
 
 
 def test_structured_synthetic_dataset_is_seeded_and_separable():

@@ -504,7 +504,7 @@ def test_bench_starts_its_own_ranks(launcher, tmp_path):
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     bench = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--model", "resnet18",
-             "--batch", "32", "--atoms", "10", "--cpu-baseline", "0"]
+             "--batch", "32", "--atoms", "10", "--full", "--cpu-baseline", "0"]
     if launcher == "self":
         cmd = [sys.executable] + bench
     else:
@@ -900,7 +900,10 @@ def test_classifier_batch_bucket_leaves_the_attack_unchanged(tmp_path):
         assert torch.equal(engine.predict(net, x), lab)
         out1, ls1, g1 = engine.input_gradient(net, x, lab, "ce", -1.0, 50.0, "mean")
         assert sizes == [8, 8] and out1.shape == out0.shape and g1.shape == g0.shape
-    close(out1, out0, 1e-6); close(g1, g0, 1e-7 + 1e-5 * float(g0.abs().max())); close(ls1, ls0, 1e-6)
+    # the padded batch can run another GEMM / convolution kernel, i.e. another summation order: equal to a few fp32 ulps
+    # of the largest logit (one ulp at |logit| = 35 is 3.8e-6), not bit for bit
+    close(out1, out0, 1e-6 * max(1.0, float(out0.abs().max()))); close(g1, g0, 1e-7 + 1e-5 * float(g0.abs().max()))
+    close(ls1, ls0, 1e-6 * max(1.0, abs(float(ls0))))
     sizes.clear()
     engine.predict(net, x)
     assert sizes == [5]                                                    # switched off again
@@ -1014,7 +1017,7 @@ def test_bench_transfer_mode_line(tmp_path):
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--mode", "transfer", "--model", "resnet18", "--batch", "4",
-                        "--atoms", "10", "--steps", "2", "--warmup", "1", "--steps-inference", "5", "--cpu-baseline", "0"],
+                        "--atoms", "10", "--steps", "2", "--warmup", "1", "--steps-inference", "5", "--full", "--cpu-baseline", "0"],
                        capture_output=True, text=True, timeout=900, cwd=str(tmp_path))
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])
@@ -1062,7 +1065,7 @@ def test_bench_inference_and_learn_mode_lines(tmp_path):
         assert len(lines) == 1
         return json.loads(lines[0])
 
-    inf = line("--mode", "inference")
+    inf = line("--mode", "inference", "--full")
     # the z-step at any real size; at 8 images x 10 atoms every launch is latency and any of the iteration's kernels can be slowest
     assert inf["roofline"]["kernel"] in ("zstep_codes_", "grad", "synth")
     # why a set and not "the z-step" (VERDICT r3 #6): at this plumbing size no launch moves more than 30 MB — every group is
@@ -1074,14 +1077,25 @@ def test_bench_inference_and_learn_mode_lines(tmp_path):
     assert "grad[z D_dagger^T]" not in inf["kernels_ms_per_step"] and "zstep_" not in inf["kernels_ms_per_step"]
     for key in ("bound", "achieved", "peak", "unit", "frac", "traffic"):
         assert key in inf["roofline"]
-    learn = line()
+    learn = line("--full")
     assert "cached" in learn["config"]["workload"] and learn["value_cached_labels"] == learn["value"]
     assert "BENCH_r02" in learn["value_definition"] and "cached" in learn["value_definition"]
     assert learn["value_reference_op_sequence_recomputed_labels"] == learn["config"]["recomputed_labels_variant"]["images_per_sec"]
     assert learn["config"]["collective"]["world_size"] == 1 and learn["config"]["collective"]["backend"] is None
-    ref = line("--cache-labels", "0")
+    ref = line("--cache-labels", "0", "--full")
     assert "recomputed" in ref["config"]["workload"] and ref["value_reference_op_sequence_recomputed_labels"] == ref["value"]
     assert ref["value_cached_labels"] == ref["config"]["cached_labels_variant"]["images_per_sec"]
+    # without --full the line is the headline alone; --dump-outputs writes what the last timed step computed
+    plain = line("--dump-outputs", str(tmp_path / "out"))
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(plain)
+    assert not {"roofline", "kernels_ms_per_step", "cpu_baseline", "value_cached_labels"} & set(plain)
+    assert "recomputed_labels_variant" not in plain["config"] and plain["steps"] == 3
+    assert abs(plain["value"] - 8 * 3 / (plain["ms_per_step"] * 3e-3)) < 1e-6 * plain["value"]
+    d, v = np.load(tmp_path / "out" / "d.npy"), np.load(tmp_path / "out" / "v.npy")
+    assert d.shape == (3, 224, 224, 10) and v.shape == (8, 10) and d.dtype == v.dtype == np.float32
+    assert np.abs(v).sum(axis=1).max() <= 8 / 255 + 1e-5                       # the codes' l1-ball projection
+    assert float(np.load(tmp_path / "out" / "fooled.npy")) == plain["config"]["train_fooling_rate_last_step"] * 8
+    assert np.isfinite(np.load(tmp_path / "out" / "loss.npy"))
 
 
 def test_resident_images_upload_through_worker_processes():

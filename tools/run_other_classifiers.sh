@@ -7,7 +7,7 @@ mkdir -p $out
 : > $out/${tag}_other_classifiers.jsonl
 run() {   # model batch atoms extra...
     m=$1; b=$2; k=$3; shift 3
-    python3 bench.py --model $m --batch $b --atoms $k --steps 6 --warmup 2 --cpu-baseline 0 "$@" 2> $out/${tag}_other_$m.err | grep "^{" >> $out/${tag}_other_classifiers.jsonl || return 1
+    python3 bench.py --model $m --batch $b --atoms $k --steps 6 --warmup 2 --full --cpu-baseline 0 "$@" 2> $out/${tag}_other_$m.err | grep "^{" >> $out/${tag}_other_classifiers.jsonl || return 1
 }
 run densenet121 512 50 || exit 1
 run vit_b_16 512 100 || exit 1

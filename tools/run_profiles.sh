@@ -14,7 +14,7 @@ python3 -c "import sys; sys.path.insert(0, '$root'); from dl_attack_on_imagenet_
 cd /tmp
 stats() {   # name, description, bench arguments...
     name=$1; desc=$2; shift 2
-    rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_$name -- python3 $root/bench.py "$@" --cpu-baseline 0 > $out/prof_${tag}_$name.log 2>&1 || return 1
+    rocprofv3 --kernel-trace --stats --output-format csv -d $out/prof_${tag}_$name -- python3 $root/bench.py "$@" --full --cpu-baseline 0 > $out/prof_${tag}_$name.log 2>&1 || return 1
     python3 $root/tools/prof_summary.py $out/prof_${tag}_$name $out/${tag}_${name}_bench_stats.md "$desc, rocprofv3 --kernel-trace --stats" > /dev/null
 }
 if [ "$phase" = "stats" ] || [ "$phase" = "all" ]; then
@@ -72,8 +72,8 @@ find $out -path "*pmc_${tag}_k*_sq*" -name "*kernel_trace.csv" -delete
 fi
 if [ "$phase" = "lines" ] || [ "$phase" = "all" ]; then
 cd $root
-python3 bench.py > $out/${tag}_bench_line.json 2> $out/${tag}_bench_line.err || exit 1
-python3 bench.py --mode inference > $out/${tag}_bench_line_inference.json 2> $out/${tag}_bench_line_inference.err || exit 1
-python3 bench.py --mode transfer > $out/${tag}_bench_line_transfer.json 2> $out/${tag}_bench_line_transfer.err || exit 1
+python3 bench.py --full > $out/${tag}_bench_line.json 2> $out/${tag}_bench_line.err || exit 1
+python3 bench.py --mode inference --full > $out/${tag}_bench_line_inference.json 2> $out/${tag}_bench_line_inference.err || exit 1
+python3 bench.py --mode transfer --full > $out/${tag}_bench_line_transfer.json 2> $out/${tag}_bench_line_transfer.err || exit 1
 fi
 echo profiles $phase done
