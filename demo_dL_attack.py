@@ -52,6 +52,10 @@ def build_parser():
                    help='validate every this many epochs (0 = after the last epoch only); the dictionary file is the same')
     p.add_argument('--upload-workers', type=int, default=0,
                    help='worker processes fetching the dataset items for the one-time upload into HBM (JPEG decoding)')
+    p.add_argument('--image-store', default='stream', choices=['stream', 'uint8'],
+                   help="how the learner keeps the training / validation images in HBM: 'stream' (default) in the stream "
+                        "dtype; 'uint8' as bytes, one per element, for 8-bit image data (ToTensor of JPEG / PIL images; "
+                        "other data is refused)")
     p.add_argument('--clean-accuracy', type=int, default=1,
                    help='1 (default, as upstream): print the clean top-1 accuracy of the classifier over the whole dataset '
                         'first (model_accuracy.py); 0 skips that pass')
@@ -138,7 +142,8 @@ def main(args):
                               data_val=val_dataset, warm_start=False, steps_inference=args.steps_inference,
                               stream_dtype=dtype if dtype != torch.float32 else None,
                               cache_labels=bool(args.cache_labels), val_every=args.val_every,
-                              upload_workers=args.upload_workers),
+                              upload_workers=args.upload_workers,
+                              image_store=None if args.image_store == 'stream' else args.image_store),
     }
     out_dir = 'dict_model_ImageNet_version_constrained'
     os.makedirs(out_dir, exist_ok=True)                                                   # quirk Q14: upstream assumes it exists

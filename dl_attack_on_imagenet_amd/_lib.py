@@ -21,6 +21,9 @@ SIGNATURES = {
     "adil_gather_images": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "adil_spd_inverse": (c_int, [c_void_p, c_int, c_void_p, c_void_p]),
     "adil_synth": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int, c_void_p]),
+    "adil_images_to_u8": (c_int, [c_void_p, c_int, c_void_p, c_size_t, c_void_p, c_void_p]),
+    "adil_synth_store": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_int,
+                                 c_void_p]),
     "adil_synth_fp8": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_float, c_int,
                                c_void_p]),
     "adil_dict_to_fp8": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
@@ -70,7 +73,7 @@ SIGNATURES = {
                                    c_void_p]),
 }
 
-ABI_VERSION = 7
+ABI_VERSION = 8
 _lib = None
 
 

@@ -72,6 +72,10 @@ class ADIL(Attack):
                      setting writes the same dictionary file; 0 = after the last epoch only.  Default 1 (as upstream)
       upload_workers worker processes that fetch the dataset items for the one-time upload into HBM (loader.ResidentImages;
                      0 = in-process, right for in-memory tensors; > 0 for datasets that decode a JPEG per item)
+      image_store    None (default): the learners keep the training / validation images resident in the stream dtype;
+                     'uint8': as bytes, one per element (a quarter of the fp32 store, half of bf16 — ImageNet train
+                     fits in 193 GB), for datasets of 8-bit images (u/255 values, ToTensor; a ValueError names the first
+                     row that is not), and every learning step synthesizes straight from the bytes (ops.synth_store)
       use_graph      replay the learning step (engine.DictionaryLearner.step_graphed) and the DDrague inference iterations
                      (engine.DDragueSolver.run, three per launch) as hipGraph launches: for launch-bound uses — small
                      batches, the one-image attack of main.py; default: $ADIL_GRAPH == "1"
@@ -84,7 +88,9 @@ class ADIL(Attack):
                  is_distributed=False, steps_in=None, loss='ce', method='gd', warm_start=False, kappa=50,
                  steps_inference=30, alpha=None, init_d=None, init_v=None, epoch_batches=None, val_batches=None,
                  stream_dtype=None, dict_dir='trained_dicts', shuffle_seed=0, use_graph=None, cache_labels=True, val_every=1,
-                 upload_workers=0):
+                 upload_workers=0, image_store=None):
+        if image_store not in (None, 'uint8'):
+            raise ValueError(f"image_store must be None or 'uint8', got {image_store!r}")
         super().__init__("ADIL", model.eval())
         self.norm = norm.lower()
         self.eps = eps
@@ -110,6 +116,7 @@ class ADIL(Attack):
         self._cache_labels = bool(cache_labels)
         self._val_every = int(val_every)
         self._upload_workers = int(upload_workers)
+        self.image_store = image_store
         self._pinv = None
         self._solvers = {}
         self._dict_mtime = None
@@ -160,7 +167,10 @@ class ADIL(Attack):
 
     def _resident(self, dataset, rows=None):
         """The data step in front of the path: the dataset (or this rank's rows of it) resident in HBM in the stream
-        dtype; replaces the per-item DataLoader of adil.py:130-133 (see loader.py)."""
+        dtype, or as bytes (image_store='uint8'); replaces the per-item DataLoader of adil.py:130-133 (see loader.py)."""
+        if self.image_store == 'uint8':
+            return ResidentImages(dataset, self.device, torch.uint8, rows=rows, num_workers=self._upload_workers,
+                                  stream_dtype=self.stream_dtype or torch.float32)
         return ResidentImages(dataset, self.device, self.stream_dtype or torch.float32, rows=rows,
                               num_workers=self._upload_workers)
 
@@ -172,10 +182,18 @@ class ADIL(Attack):
         return shuffled_batches(n, batch_size)
 
     def _labelled_batches(self, train, order):
-        """(index, x, labels) per batch; labels is None (the learner recomputes them, adil.py:172) unless cache_labels."""
+        """(index, x, labels) per batch; labels is None (the learner recomputes them, adil.py:172) unless cache_labels.
+        For an 8-bit store x is the store itself (the learner synthesizes from its rows `index`); a clean batch is
+        gathered only for a label that is not cached yet."""
         order = [list(idx) for idx in order]
         if self._cache_labels and getattr(train, "_label_cache", None) is None:
             train._label_cache = engine.LabelCache(len(train), self.device)
+        if getattr(train, "is_bytes", False):
+            for rows in order:
+                index = train.index_tensor(rows)
+                yield index, train, (train._label_cache.get(self.model, lambda index=index: train.gather(index), index, rows)
+                                     if self._cache_labels and len(rows) else None)
+            return
         for rows, (index, x) in zip(order, train.batches(order)):
             yield index, x, (train._label_cache.get(self.model, x, index, rows) if self._cache_labels and len(rows) else None)
 

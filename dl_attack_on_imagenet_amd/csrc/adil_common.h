@@ -27,6 +27,11 @@ __device__ __forceinline__ unsigned pack2_bf16(float a, float b) {
     return __builtin_bit_cast(unsigned, __builtin_convertvector(v, adil_bf16x2));
 }
 
+// Value of byte u of an 8-bit image store (ADIL_U8): u/255 CORRECTLY rounded, bitwise torch's `u8.float().div(255)`.
+// Plain IEEE division (hipcc's default for fp32 `/`; the library is built without fast-math).  u * (1/255.f) is not it:
+// it differs in 126 of the 256 values.
+__device__ __forceinline__ float u8_unit(unsigned u) { return (float)u / 255.0f; }
+
 template <typename T> struct Elem;
 template <> struct Elem<float> {
     static __device__ __forceinline__ float load(const float* p, size_t i) { return p[i]; }

@@ -13,6 +13,7 @@
 // C/D layout of a 32x32 tile: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 #include <cstdlib>
 #include <mutex>
+#include <type_traits>
 #include <unordered_map>
 
 #include "adil_common.h"
@@ -345,6 +346,31 @@ template <> struct BufPx<bf16_t> {
     }
 };
 
+// The x rows of adil_synth_store: row b of the batch is row index[b] of an R x P 8-bit image store, byte u standing for
+// u8_unit(u) (looked up in a 256-entry LDS table).  R * P may exceed 4 GB, so a row's offset is formed in 64 bits and
+// the bytes come through a global load, never through a 32-bit buffer offset.  4 consecutive pixels = one dword (P % 8
+// == 0, the store 4-byte aligned); rows >= B read row B-1 (they are never stored).
+struct StoreRows {
+    const unsigned char* st;
+    const int64_t* idx;
+    const float* tab;
+    int B, P;
+    __device__ __forceinline__ unsigned raw4(int row, int px) const {
+        const int64_t r = idx[row < B ? row : B - 1];
+        return *reinterpret_cast<const unsigned*>(st + r * (int64_t)P + px);
+    }
+    __device__ __forceinline__ void unpack(unsigned t, float (&o)[4]) const {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] = tab[(t >> (8 * i)) & 255u];
+    }
+    // the element-wise tiles: px may lie past the row end (a whole group of 4 does, P % 4 == 0) -> zeros
+    __device__ __forceinline__ void load4(int row, int px, float (&o)[4]) const {
+        unpack(raw4(row, px < P ? px : P - 4), o);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) o[i] *= (px < P) ? 1.0f : 0.0f;
+    }
+};
+
 // 8 consecutive fp32 values (16-B aligned, e.g. a row of the packed codes) as an MFMA fragment
 template <typename T>
 __device__ __forceinline__ typename Mma<T>::Frag frag_from_f32x8(const float* p, float scale = 1.0f) {
@@ -378,10 +404,11 @@ __device__ __forceinline__ int c_row(int reg, int h) { return (reg & 3) + 8 * (r
 // =========================================================================================================== //
 #define SYNTH_TILE 128
 
-template <typename T, typename O, bool XACC, bool FAST>
+template <typename T, typename O, bool XACC, bool FAST, bool STORE = false>
 __device__ __forceinline__ void synth_sweep(const T* __restrict__ x, const float* __restrict__ vp, T* __restrict__ out,
                                             const typename DImg<O>::Elem* sd, int B, int P, int Kp, int Ks, int p0,
-                                            float delta_clamp, int pixel_clamp, int w, int c, int h, OpScale sc) {
+                                            float delta_clamp, int pixel_clamp, int w, int c, int h, OpScale sc,
+                                            StoreRows srows = {}) {
     using M = Mma<O>;
     using Frag = typename M::Frag;
     const int plane = SYNTH_TILE * Ks;
@@ -397,7 +424,8 @@ __device__ __forceinline__ void synth_sweep(const T* __restrict__ x, const float
             float xv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
             if (XACC) {
                 const int row = b0 + c_row(reg, h);
-                load_px<T, 4, FAST>(x + (size_t)(row < B ? row : B - 1) * P, px, P, xv);   // rows >= B are never stored
+                if constexpr (STORE) srows.load4(row, px, xv);
+                else load_px<T, 4, FAST>(x + (size_t)(row < B ? row : B - 1) * P, px, P, xv);   // rows >= B are never stored
             }
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t][reg] = M::SCALED ? xv[t] * xs : xv[t];
@@ -427,7 +455,8 @@ __device__ __forceinline__ void synth_sweep(const T* __restrict__ x, const float
                 }
                 if (x != nullptr) {
                     float xv[4];
-                    load_px<T, 4, FAST>(x + (size_t)(row < B ? row : B - 1) * P, px, P, xv);
+                    if constexpr (STORE) srows.load4(row, px, xv);
+                    else load_px<T, 4, FAST>(x + (size_t)(row < B ? row : B - 1) * P, px, P, xv);
 #pragma unroll
                     for (int t = 0; t < 4; ++t) r[t] += xv[t];
                 }
@@ -441,9 +470,10 @@ __device__ __forceinline__ void synth_sweep(const T* __restrict__ x, const float
     }
 }
 
-template <typename T, bool XACC, bool PIXCLAMP, bool SCALED>
+template <typename T, bool XACC, bool PIXCLAMP, bool SCALED, bool STORE = false>
 __device__ __forceinline__ void synth_store_buf(const f32x16 (&acc)[4], buf_rsrc rx, buf_rsrc ro, int voff, unsigned rowb,
-                                                float delta_clamp, float oscale) {
+                                                float delta_clamp, float oscale, const StoreRows& srows = {}, int row0 = 0,
+                                                int px = 0) {
     using BP = BufPx<T>;
 #pragma unroll
     for (int reg = 0; reg < 16; ++reg) {
@@ -457,7 +487,8 @@ __device__ __forceinline__ void synth_store_buf(const f32x16 (&acc)[4], buf_rsrc
                 for (int t = 0; t < 4; ++t) r[t] = fminf(fmaxf(r[t], -delta_clamp), delta_clamp);
             }
             float xv[4];
-            BP::unpack(BP::load(rx, voff, soff), xv);                                     // x == NULL: empty buffer -> 0
+            if constexpr (STORE) srows.unpack(srows.raw4(row0 + c_row(reg, 0), px), xv);
+            else BP::unpack(BP::load(rx, voff, soff), xv);                                // x == NULL: empty buffer -> 0
 #pragma unroll
             for (int t = 0; t < 4; ++t) r[t] += xv[t];
         }
@@ -474,11 +505,12 @@ __device__ __forceinline__ void synth_store_buf(const f32x16 (&acc)[4], buf_rsrc
 // for its codes (hidden under the HBM latency of x) instead of one per k-group in the MFMA loop.
 // HOIST = 4 covers K <= 64; K > 64 runs the HOIST = 8 instantiation (all k-groups up front; costs ~45 registers, i.e. one
 // resident workgroup per CU less, which the K <= 64 stream cannot afford)
-template <typename T, typename O, bool XACC, int HOIST, int NWV = 4>
+// STORE: the x rows come from an 8-bit store (StoreRows) through global loads; out still goes through buffers.
+template <typename T, typename O, bool XACC, int HOIST, int NWV = 4, bool STORE = false>
 __device__ __forceinline__ void synth_sweep_buf(const T* __restrict__ x, const float* __restrict__ vp,
                                                 T* __restrict__ out, const typename DImg<O>::Elem* sd, int B, int P,
                                                 int Kp, int Ks, int p0, float delta_clamp, int pixel_clamp, int w, int c,
-                                                int h, OpScale sc) {
+                                                int h, OpScale sc, StoreRows srows = {}) {
     using M = Mma<O>;
     using Frag = typename M::Frag;
     using BP = BufPx<T>;
@@ -490,12 +522,16 @@ __device__ __forceinline__ void synth_sweep_buf(const T* __restrict__ x, const f
     for (int bb = w; bb < nbb; bb += NWV) {
         const int b0 = bb << 5;
         const int rows = B - b0 < 32 ? B - b0 : 32;
-        const buf_rsrc rx = block_rsrc(x ? x + (size_t)b0 * P : nullptr, x ? (unsigned)rows * rowb : 0u);
+        const bool xbuf = !STORE && x;
+        const buf_rsrc rx = block_rsrc(xbuf ? x + (size_t)b0 * P : nullptr, xbuf ? (unsigned)rows * rowb : 0u);
         const buf_rsrc ro = block_rsrc(out + (size_t)b0 * P, (unsigned)rows * rowb);
-        typename BP::Raw xr[16];
+        typename std::conditional<STORE, unsigned, typename BP::Raw>::type xr[16];
         if (XACC) {
 #pragma unroll
-            for (int reg = 0; reg < 16; ++reg) xr[reg] = BP::load(rx, voff, (int)((unsigned)c_row(reg, 0) * rowb));
+            for (int reg = 0; reg < 16; ++reg) {
+                if constexpr (STORE) xr[reg] = srows.raw4(b0 + 4 * h + c_row(reg, 0), p0 + 4 * c);
+                else xr[reg] = BP::load(rx, voff, (int)((unsigned)c_row(reg, 0) * rowb));
+            }
         }
         const float* arow = vp + (size_t)(b0 + c) * Kp + 8 * h;
         float4 araw[HOIST][2];
@@ -527,7 +563,10 @@ __device__ __forceinline__ void synth_sweep_buf(const T* __restrict__ x, const f
 #pragma unroll
         for (int reg = 0; reg < 16; ++reg) {
             float xv[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-            if (XACC) BP::unpack(xr[reg], xv);
+            if (XACC) {
+                if constexpr (STORE) srows.unpack(xr[reg], xv);
+                else BP::unpack(xr[reg], xv);
+            }
 #pragma unroll
             for (int t = 0; t < 4; ++t) acc[t][reg] = M::SCALED ? xv[t] * (sc.v * sc.d) : xv[t];
         }
@@ -544,9 +583,11 @@ __device__ __forceinline__ void synth_sweep_buf(const T* __restrict__ x, const f
             for (int t = 0; t < 4; ++t) M::mma(acc[t], ag, DImg<O>::load8(sd + (t * 32 + c) * Ks + 16 * g + 8 * h, plane));
         }
         if (pixel_clamp)                                                                  // uniform: one branch per block
-            synth_store_buf<T, XACC, true, M::SCALED>(acc, rx, ro, voff, rowb, delta_clamp, sc.o);
+            synth_store_buf<T, XACC, true, M::SCALED, STORE>(acc, rx, ro, voff, rowb, delta_clamp, sc.o, srows, b0 + 4 * h,
+                                                             p0 + 4 * c);
         else
-            synth_store_buf<T, XACC, false, M::SCALED>(acc, rx, ro, voff, rowb, delta_clamp, sc.o);
+            synth_store_buf<T, XACC, false, M::SCALED, STORE>(acc, rx, ro, voff, rowb, delta_clamp, sc.o, srows, b0 + 4 * h,
+                                                              p0 + 4 * c);
     }
 }
 
@@ -660,11 +701,13 @@ __device__ __forceinline__ void fill_dict_slice_fp8(const unsigned char* __restr
         for (int k = K + (tid & 1); k < Kp; k += 2) sd[(((tid >> 1) & 3) * 32 + (tid >> 3)) * Ks + k] = 0;   // e4m3 0x00 = +0
 }
 
-template <typename T, typename O, bool XACC, bool FAST, int HOIST = 4, int NWV = 4, bool PACKED = false>
+// STORE (adil_synth_store): `x` is the 8-bit image store (bytes, R x P) and `xidx` the batch's B rows of it; the 256-entry
+// value table sits in LDS behind the D planes.
+template <typename T, typename O, bool XACC, bool FAST, int HOIST = 4, int NWV = 4, bool PACKED = false, bool STORE = false>
 __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV == 4 ? 3 : 2))) void synth_mfma_kernel(const T* __restrict__ x, const float* __restrict__ d,
                                                          const float* __restrict__ vp, T* __restrict__ out, int B,
                                                          int P, int K, int Kp, float delta_clamp, int pixel_clamp,
-                                                         int tile0, OpScale sc) {
+                                                         int tile0, OpScale sc, const int64_t* __restrict__ xidx = nullptr) {
     using DE = typename DImg<O>::Elem;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     DE* sd = reinterpret_cast<DE*>(smem_raw);                    // [PLANES][128][Ks] bf16 (fp8: bytes)
@@ -678,12 +721,18 @@ __global__ __launch_bounds__(NWV * 64) __attribute__((amdgpu_waves_per_eu(NWV ==
         fill_dict_slice_fp8<NWV * 64>(reinterpret_cast<const unsigned char*>(d), reinterpret_cast<unsigned char*>(sd), p0, K, Kp, Ks, tid);
     else
         fill_dict_slice<O, FAST, NWV * 64>(d, sd, p0, P, K, Kp, Ks, tid, sc.d);
+    StoreRows srows = {};
+    if constexpr (STORE) {
+        float* tab = reinterpret_cast<float*>(smem_raw + (size_t)DImg<O>::PLANES * plane * sizeof(DE));
+        if (tid < 256) tab[tid] = u8_unit(tid);
+        srows = StoreRows{reinterpret_cast<const unsigned char*>(x), xidx, tab, B, P};
+    }
     __syncthreads();
     if constexpr (FAST)
-        synth_sweep_buf<T, O, XACC, HOIST, NWV>(x, vp, out, sd, B, P, Kp, Ks, p0, delta_clamp, pixel_clamp,
-                                    __builtin_amdgcn_readfirstlane(w), c, h, sc);
+        synth_sweep_buf<T, O, XACC, HOIST, NWV, STORE>(x, vp, out, sd, B, P, Kp, Ks, p0, delta_clamp, pixel_clamp,
+                                    __builtin_amdgcn_readfirstlane(w), c, h, sc, srows);
     else
-        synth_sweep<T, O, XACC, FAST>(x, vp, out, sd, B, P, Kp, Ks, p0, delta_clamp, pixel_clamp, w, c, h, sc);
+        synth_sweep<T, O, XACC, FAST, STORE>(x, vp, out, sd, B, P, Kp, Ks, p0, delta_clamp, pixel_clamp, w, c, h, sc, srows);
 }
 
 // =========================================================================================================== //
@@ -2122,36 +2171,38 @@ extern "C" size_t adil_grad_workspace_bytes(int B, int P, int K) {
     return ((vpt + 255) / 256) * 256 + slab;
 }
 
-template <typename T, typename O, bool XACC, bool FAST>
+template <typename T, typename O, bool XACC, bool FAST, bool STORE = false>
 static int launch_synth_range(const void* x, const float* d, const float* vp, void* out, int B, int P, int K,
-                              float delta_clamp, int pixel_clamp, int tile0, int ntiles, OpScale sc, hipStream_t st) {
+                              float delta_clamp, int pixel_clamp, int tile0, int ntiles, OpScale sc, hipStream_t st,
+                              const int64_t* xidx = nullptr) {
     if (ntiles <= 0) return 0;
     const int Kp = round_up(K, 16);
-    const size_t lds = (size_t)DImg<O>::PLANES * SYNTH_TILE * (Kp + DPAD) * sizeof(typename DImg<O>::Elem);
+    const size_t lds = (size_t)DImg<O>::PLANES * SYNTH_TILE * (Kp + DPAD) * sizeof(typename DImg<O>::Elem) +
+                       (STORE ? 256 * sizeof(float) : 0);     // + the byte -> value table of an 8-bit store
     if constexpr (FAST && sizeof(typename Mma<O>::Frag) <= 16) {      // (fp32 operands: 12 registers per split fragment, 8 do not fit)
         if (Kp > 64) {                                            // all k-groups' code fragments hoisted (see synth_sweep_buf)
-            int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, true, 8>, lds);
+            int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, true, 8, 4, false, STORE>, lds);
             if (rc) return rc;
-            hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, true, 8>), dim3(ntiles), dim3(256), lds, st, (const T*)x, d, vp,
-                               (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc);
+            hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, true, 8, 4, false, STORE>), dim3(ntiles), dim3(256), lds, st, (const T*)x, d, vp,
+                               (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc, xidx);
             ADIL_CHECK_LAUNCH();
             return 0;
         }
     }
     if constexpr (FAST && sizeof(typename Mma<O>::Frag) > 16) {
         if (Kp > 64) {      // fp32 operands, K > 64: 92 KB of D planes = one workgroup per CU, so give it 8 waves instead of 4
-            int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, true, 4, 8>, lds);
+            int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, true, 4, 8, false, STORE>, lds);
             if (rc) return rc;
-            hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, true, 4, 8>), dim3(ntiles), dim3(512), lds, st, (const T*)x, d, vp,
-                               (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc);
+            hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, true, 4, 8, false, STORE>), dim3(ntiles), dim3(512), lds, st, (const T*)x, d, vp,
+                               (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc, xidx);
             ADIL_CHECK_LAUNCH();
             return 0;
         }
     }
-    int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, FAST>, lds);
+    int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, FAST, 4, 4, false, STORE>, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, FAST>), dim3(ntiles), dim3(256), lds, st, (const T*)x, d, vp, (T*)out,
-                       B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc);
+    hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, FAST, 4, 4, false, STORE>), dim3(ntiles), dim3(256), lds, st, (const T*)x, d, vp, (T*)out,
+                       B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc, xidx);
     ADIL_CHECK_LAUNCH();
     return 0;
 }
@@ -2168,6 +2219,22 @@ static int launch_synth_x(const void* x, const float* d, const float* vp, void* 
     int rc = launch_synth_range<T, O, XACC, true>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, 0, nfast, sc, st);
     if (rc) return rc;
     return launch_synth_range<T, O, XACC, false>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, nfast, ntiles - nfast, sc, st);
+}
+
+// adil_synth_store: the same tile split, x read out of the 8-bit store (never through buffer instructions, so only out
+// and d decide which tiles are FAST)
+template <typename T, bool XACC>
+static int launch_synth_store(const uint8_t* store, const int64_t* index, const float* d, const float* vp, void* out, int B,
+                              int P, int K, float delta_clamp, int pixel_clamp, hipStream_t st) {
+    const OpScale one{1.0f, 1.0f, 1.0f};
+    const bool vec = (((uintptr_t)out | (uintptr_t)d) % 16 == 0) && (P <= (1 << 23));
+    const int ntiles = (P + SYNTH_TILE - 1) / SYNTH_TILE;
+    const int nfast = vec ? P / SYNTH_TILE : 0;
+    int rc = launch_synth_range<T, T, XACC, true, true>(store, d, vp, out, B, P, K, delta_clamp, pixel_clamp, 0, nfast, one,
+                                                         st, index);
+    if (rc) return rc;
+    return launch_synth_range<T, T, XACC, false, true>(store, d, vp, out, B, P, K, delta_clamp, pixel_clamp, nfast,
+                                                        ntiles - nfast, one, st, index);
 }
 
 template <typename T>
@@ -2246,6 +2313,22 @@ extern "C" int adil_synth(const void* x, const float* d, const float* vp, void* 
     if (!d || !vp || !out || B <= 0 || P <= 0 || K <= 0 || K > ADIL_MAX_ATOMS) return ADIL_EINVAL;
     if (dtype == ADIL_F32) return launch_synth<float>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, (hipStream_t)stream);
     if (dtype == ADIL_BF16) return launch_synth<bf16_t>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, (hipStream_t)stream);
+    return ADIL_EINVAL;
+}
+
+extern "C" int adil_synth_store(const uint8_t* store, const int64_t* index, const float* d, const float* vp, void* out, int B,
+                                int P, int K, int out_dtype, float delta_clamp, int pixel_clamp, void* stream) {
+    ADIL_ENTER();
+    if (!store || !index || !d || !vp || !out || B <= 0 || P <= 0 || (P & 7) || K <= 0 || K > ADIL_MAX_ATOMS) return ADIL_EINVAL;
+    if ((uintptr_t)store & 3) return ADIL_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    const bool xacc = delta_clamp < 0.0f;                         // as adil_synth with x present
+    if (out_dtype == ADIL_F32)
+        return xacc ? launch_synth_store<float, true>(store, index, d, vp, out, B, P, K, delta_clamp, pixel_clamp, st)
+                    : launch_synth_store<float, false>(store, index, d, vp, out, B, P, K, delta_clamp, pixel_clamp, st);
+    if (out_dtype == ADIL_BF16)
+        return xacc ? launch_synth_store<bf16_t, true>(store, index, d, vp, out, B, P, K, delta_clamp, pixel_clamp, st)
+                    : launch_synth_store<bf16_t, false>(store, index, d, vp, out, B, P, K, delta_clamp, pixel_clamp, st);
     return ADIL_EINVAL;
 }
 

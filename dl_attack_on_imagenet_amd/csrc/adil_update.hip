@@ -255,7 +255,8 @@ __global__ __launch_bounds__(256) void pack_codes_kernel(const float* __restrict
 
 // ---- batched image gather (the data step in front of the path) -------------- //
 // dst[b][:] = convert(src[index[b]][:]); 8 elements per thread: 16-byte accesses on the 2-byte side, 2 x 16 B on the
-// 4-byte side.  P % 8 == 0.  One pass: B*P*(sizeof(S)+sizeof(D)) bytes.
+// 4-byte side, 8 B on the byte side (an 8-bit store: u -> u8_unit(u)).  P % 8 == 0.  One pass: B*P*(sizeof(S)+sizeof(D))
+// bytes.
 template <typename S, typename D>
 __global__ __launch_bounds__(256) void gather_images_kernel(const S* __restrict__ src, const int64_t* __restrict__ index,
                                                             D* __restrict__ dst, int B, int P8) {
@@ -268,6 +269,10 @@ __global__ __launch_bounds__(256) void gather_images_kernel(const S* __restrict_
         if constexpr (sizeof(S) == 4) {
             const float4 a = reinterpret_cast<const float4*>(s)[2 * i], c = reinterpret_cast<const float4*>(s)[2 * i + 1];
             f[0] = a.x; f[1] = a.y; f[2] = a.z; f[3] = a.w; f[4] = c.x; f[5] = c.y; f[6] = c.z; f[7] = c.w;
+        } else if constexpr (sizeof(S) == 1) {
+            const uint2 a = reinterpret_cast<const uint2*>(s)[i];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) { f[j] = u8_unit((a.x >> (8 * j)) & 255u); f[4 + j] = u8_unit((a.y >> (8 * j)) & 255u); }
         } else {
             const uint4 a = reinterpret_cast<const uint4*>(s)[i];
             const unsigned w[4] = {a.x, a.y, a.z, a.w};
@@ -283,6 +288,30 @@ __global__ __launch_bounds__(256) void gather_images_kernel(const S* __restrict_
             reinterpret_cast<uint4*>(d)[i] = o;
         }
     }
+}
+
+// ---- fp32 images -> an 8-bit store, with the check that they ARE 8-bit ---------------------------------------- //
+// dst[i] = rint(255 src[i]) clamped to [0, 255]; an element whose fp32 bits differ from u8_unit(dst[i]) is counted (NaN,
+// values outside [0, 1], -0, anything between two u/255).  8 elements per thread; one counter add per wave that saw any.
+__global__ __launch_bounds__(256) void images_to_u8_kernel(const float* __restrict__ src, uint2* __restrict__ dst, size_t n8,
+                                                           unsigned long long* __restrict__ mismatches) {
+    unsigned bad = 0;
+    const size_t stride = (size_t)gridDim.x * blockDim.x;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n8; i += stride) {
+        const float4 a = reinterpret_cast<const float4*>(src)[2 * i], c = reinterpret_cast<const float4*>(src)[2 * i + 1];
+        const float f[8] = {a.x, a.y, a.z, a.w, c.x, c.y, c.z, c.w};
+        unsigned w[2] = {0u, 0u};
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const unsigned u = (unsigned)fminf(fmaxf(rintf(f[j] * 255.0f), 0.0f), 255.0f);
+            bad += (__float_as_uint(u8_unit(u)) != __float_as_uint(f[j])) ? 1u : 0u;
+            w[j >> 2] |= u << (8 * (j & 3));
+        }
+        dst[i] = make_uint2(w[0], w[1]);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) bad += __shfl_xor(bad, o, 64);
+    if ((threadIdx.x & 63) == 0 && bad != 0) atomicAdd(mismatches, (unsigned long long)bad);   // global atomic, vector lane
 }
 
 // ---- K7: inverse of the K x K Gram matrix (symmetric positive definite) ------ //
@@ -508,7 +537,7 @@ static inline int stream_grid(size_t work_items, int per_block) {
     return (int)b;
 }
 
-extern "C" int adil_abi_version(void) { return 7; }
+extern "C" int adil_abi_version(void) { return 8; }
 extern "C" int adil_max_atoms(void) { return ADIL_MAX_ATOMS; }
 
 extern "C" int adil_pack_codes(const float* v, const int64_t* index, int B, int K, float* vp, int32_t* pos, void* vpt,
@@ -552,8 +581,24 @@ extern "C" int adil_gather_images(const void* src, int src_dtype, const int64_t*
         hipLaunchKernelGGL((gather_images_kernel<bf16_t, float>), grid, block, 0, st, (const bf16_t*)src, index, (float*)dst, B, P8);
     else if (src_dtype == ADIL_BF16 && dst_dtype == ADIL_BF16)
         hipLaunchKernelGGL((gather_images_kernel<bf16_t, bf16_t>), grid, block, 0, st, (const bf16_t*)src, index, (bf16_t*)dst, B, P8);
+    else if (src_dtype == ADIL_U8 && dst_dtype == ADIL_F32)
+        hipLaunchKernelGGL((gather_images_kernel<uint8_t, float>), grid, block, 0, st, (const uint8_t*)src, index, (float*)dst, B, P8);
+    else if (src_dtype == ADIL_U8 && dst_dtype == ADIL_BF16)
+        hipLaunchKernelGGL((gather_images_kernel<uint8_t, bf16_t>), grid, block, 0, st, (const uint8_t*)src, index, (bf16_t*)dst, B, P8);
     else
         return ADIL_EINVAL;
+    ADIL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int adil_images_to_u8(const void* src, int src_dtype, uint8_t* dst, size_t n, unsigned long long* mismatches,
+                                 void* stream) {
+    ADIL_ENTER();
+    if (!src || !dst || !mismatches || src_dtype != ADIL_F32 || n == 0 || (n & 7)) return ADIL_EINVAL;
+    if (((uintptr_t)src & 15) || ((uintptr_t)dst & 7) || ((uintptr_t)mismatches & 7)) return ADIL_EINVAL;
+    const size_t n8 = n / 8;
+    hipLaunchKernelGGL(images_to_u8_kernel, dim3(stream_grid(n8, 256)), dim3(256), 0, (hipStream_t)stream, (const float*)src,
+                       (uint2*)dst, n8, mismatches);
     ADIL_CHECK_LAUNCH();
     return 0;
 }

@@ -130,6 +130,16 @@ def input_gradient(model, xt: Tensor, labels: Tensor, loss: str, coeff: float, k
     return out.detach(), ls.detach(), g.contiguous()
 
 
+def _is_byte_store(x) -> bool:
+    """x is an 8-bit image store (loader.ResidentImages(dtype=torch.uint8)) handed to a learning step in place of a
+    batch: the step's `index` then names its rows, and the synthesis reads them straight out of it."""
+    return getattr(x, "is_bytes", False)
+
+
+def _batch_rows(x, index: Tensor) -> int:
+    return index.numel() if _is_byte_store(x) else x.shape[0]
+
+
 def _flat_images(x: Tensor) -> Tensor:
     if x.dim() != 4:
         raise ValueError(f"images must be (B,C,H,W), got {tuple(x.shape)}")
@@ -153,12 +163,13 @@ class LabelCache:
         self.labels = torch.full((n,), -1, dtype=torch.int64, device=device)
         self._known = [False] * n
 
-    def get(self, model, x: Tensor, index: Tensor, rows) -> Tensor:
-        """Labels of the batch `x` = resident rows `rows` (host ints; `index` is the same on the device)."""
+    def get(self, model, x, index: Tensor, rows) -> Tensor:
+        """Labels of the batch `x` = resident rows `rows` (host ints; `index` is the same on the device).  `x` may be a
+        callable that forms the batch: it is called only when a label has to be computed."""
         rows = [int(r) for r in rows]
         if all(self._known[r] for r in rows):
             return self.labels[index]
-        lab = predict(model, x)
+        lab = predict(model, x() if callable(x) else x)
         self.labels[index] = lab
         for r in rows:
             self._known[r] = True
@@ -172,7 +183,10 @@ class DictionaryLearner:
     d: (C,H,W,K) fp32, v: (N,K) fp32 (updated in place), each with AdamW moments.
     `lr_d`/`lr_v` default to the single-optimiser setting of learn_dictionary_a (adil.py:154).
     With a DictGradReducer the rows of v are the LOCAL shard and grad_d is summed over ranks
-    (one all-reduce per step) before the identical AdamW update on every rank."""
+    (one all-reduce per step) before the identical AdamW update on every rank.
+    The steps take a batch `x` (B,C,H,W) or an 8-bit image store (loader.ResidentImages(dtype=torch.uint8)) with
+    `index` its rows: the synthesis then reads the rows straight out of the store (ops.synth_store, in the store's
+    stream dtype), and the clean batch is gathered only when a label has to be computed."""
 
     def __init__(self, d: Tensor, v: Tensor, eps: float, step_size: float = 0.01, loss: str = "ce",
                  targeted: bool = False, kappa: float = 50.0, lr_d: Optional[float] = None,
@@ -210,12 +224,17 @@ class DictionaryLearner:
         """K1: x + D v[index] (adil.py:25-26).  Returns (xt, codes) with `codes` what backward() needs: the gather of
         the batch's code rows also records their batch slots in `pos` (consumed + reset by update_v) and, for a D-step,
         writes the transposed copy in the stream dtype that the grad_d contraction reads."""
-        b = x.shape[0]
-        vp = ops.pack_codes(self.v, index, b, pos=self.pos if want_v else None, transposed=x.dtype if want_d else None)
+        store = _is_byte_store(x)
+        b = _batch_rows(x, index)
+        sdt = x.stream_dtype if store else x.dtype
+        vp = ops.pack_codes(self.v, index, b, pos=self.pos if want_v else None, transposed=sdt if want_d else None)
         vpt = None
         if want_d:
             vp, vpt = vp
-        xt = ops.synth(_flat_images(x), self.d, vp, b, fp8_absmax=self.fp8_absmax, d_fp8=self.d_fp8)
+        if store:
+            xt = ops.synth_store(x.images, index, self.d, vp, b, sdt)
+        else:
+            xt = ops.synth(_flat_images(x), self.d, vp, b, fp8_absmax=self.fp8_absmax, d_fp8=self.d_fp8)
         return xt, (vp, vpt, b)
 
     def backward(self, g: Tensor, codes, want_d: bool = True, want_v: bool = True):
@@ -231,8 +250,8 @@ class DictionaryLearner:
             self._pending = self.reducer.all_reduce_start(gd)
         return gd, gvb
 
-    def forward_backward(self, model, x: Tensor, index: Tensor, labels: Tensor, want_d: bool, want_v: bool):
-        if x.shape[0] == 0:
+    def forward_backward(self, model, x, index: Tensor, labels: Tensor, want_d: bool, want_v: bool):
+        if _batch_rows(x, index) == 0:
             return self._empty_batch(x, want_d)
         xt, codes = self.synthesize(x, index, want_d, want_v)                            # K1
         out, ls, g = input_gradient(model, xt, labels, self.loss, self.coeff, self.kappa, "sum")
@@ -276,7 +295,7 @@ class DictionaryLearner:
                           dyn=self._dyn_v)
 
     # -- the whole step as ONE hipGraph launch (launch-bound configurations) ------------------------------------ #
-    def step_graphed(self, model, x: Tensor, index: Tensor, labels: Optional[Tensor] = None):
+    def step_graphed(self, model, x, index: Tensor, labels: Optional[Tensor] = None):
         """`step()` replayed from a hipGraph: the ~200 launches of a step (classifier forward twice, backward, the five
         ADiL kernels) become one graph launch — for launch-bound uses (small crops, tiny classifiers; configs[0] itself,
         resnet18 on 32 images of 224x224, turned out GPU-bound: 7.2 ms either way).  The first two calls run eagerly (library autotuning must not
@@ -284,12 +303,16 @@ class DictionaryLearner:
         into the graph's static inputs and replay.  AdamW's step-dependent scalars reach the recorded launches through
         device memory (`dyn_scalars`).  `labels`: the cached clean pseudo-labels of the batch (engine.LabelCache); the
         recording then holds one classifier forward less.  A different batch size, a change between given and recomputed
-        labels, a reducer (the collective is not captured) or an empty batch falls back to the eager step.  Results are
+        labels, a reducer (the collective is not captured) or an empty batch falls back to the eager step.  With an
+        8-bit store as `x` the recording holds the store's pointer and takes the rows from a static index buffer (a
+        different store falls back to the eager step as well).  Results are
         bit-identical to `step()` (tests/test_gpu_adil.py)."""
         index = index.to(device=self.v.device, dtype=torch.int64)
-        b = x.shape[0]
+        store = _is_byte_store(x)
+        b = _batch_rows(x, index)
         if self.reducer is not None or b == 0 or (self._graph is not None and
-                                                  (self._graph[5] != b or (self._graph[6] is None) != (labels is None))):
+                                                  (self._graph[5] != b or (self._graph[6] is None) != (labels is None) or
+                                                   ((store or _is_byte_store(self._graph[1])) and self._graph[1] is not x))):
             return self.step(model, x, index, labels)
         if self._graph is None:
             if self._graph_warm < 2:
@@ -297,7 +320,7 @@ class DictionaryLearner:
                 return self.step(model, x, index, labels)
             self._dyn_d = self.sched_d.enable_device_scalars(self.d.device)
             self._dyn_v = self.sched_v.enable_device_scalars(self.v.device)
-            gx, gi = x.clone(), index.clone()
+            gx, gi = (x if store else x.clone()), index.clone()   # a store: its pointer is recorded, its rows via gi
             gl = labels.clone() if labels is not None else None
             t_d, t_v = self.sched_d.t, self.sched_v.t
             graph = torch.cuda.CUDAGraph()
@@ -306,7 +329,8 @@ class DictionaryLearner:
             self.sched_d.t, self.sched_v.t = t_d, t_v            # capture records, it does not execute: no step was taken
             self._graph = (graph, gx, gi, ls, fooled, b, gl)
         graph, gx, gi, ls, fooled, _, gl = self._graph
-        gx.copy_(x)
+        if not store:
+            gx.copy_(x)
         gi.copy_(index)
         if gl is not None:
             gl.copy_(labels)
@@ -316,30 +340,41 @@ class DictionaryLearner:
         return ls.clone(), fooled.clone()
 
     # -- reference loops ---------------------------------------------------- #
-    def step(self, model, x: Tensor, index: Tensor, labels: Optional[Tensor] = None):
+    def _clean_batch(self, x, index: Tensor) -> Tensor:
+        """The clean batch for a label: x itself, or its rows gathered out of a store."""
+        return x.gather(index) if _is_byte_store(x) else x
+
+    def _check_source(self, x) -> None:
+        if _is_byte_store(x) and self.fp8_absmax is not None:
+            raise ValueError("DictionaryLearner: the fp8 synthesis (fp8_synth=True) cannot read an 8-bit image store")
+
+    def step(self, model, x, index: Tensor, labels: Optional[Tensor] = None):
         """learn_dictionary_a hot-loop body (adil.py:168-191). Returns (loss, #fooled) as 0-d device tensors."""
+        self._check_source(x)
         index = index.to(device=self.v.device, dtype=torch.int64)
-        if labels is None and x.shape[0]:
-            labels = predict(model, x)                                                   # adil.py:172
+        if labels is None and _batch_rows(x, index):
+            labels = predict(model, self._clean_batch(x, index))                          # adil.py:172
         ls, fooled, gd, gvb = self.forward_backward(model, x, index, labels, True, True)
         self.update_v(gvb)                                       # overlaps with the all-reduce of grad_d (if any)
         self.update_d(gd)
         return ls, fooled
 
-    def step_codes(self, model, x: Tensor, index: Tensor, labels: Optional[Tensor] = None):
+    def step_codes(self, model, x, index: Tensor, labels: Optional[Tensor] = None):
         """V-step of learn_dictionary_b (adil.py:268-287)."""
+        self._check_source(x)
         index = index.to(device=self.v.device, dtype=torch.int64)
         if labels is None:
-            labels = predict(model, x)
+            labels = predict(model, self._clean_batch(x, index))
         ls, fooled, _, gvb = self.forward_backward(model, x, index, labels, False, True)
         self.update_v(gvb)
         return ls, fooled
 
-    def step_dictionary(self, model, x: Tensor, index: Tensor, labels: Optional[Tensor] = None):
+    def step_dictionary(self, model, x, index: Tensor, labels: Optional[Tensor] = None):
         """D-step of learn_dictionary_b (adil.py:295-311)."""
+        self._check_source(x)
         index = index.to(device=self.v.device, dtype=torch.int64)
         if labels is None:
-            labels = predict(model, x)
+            labels = predict(model, self._clean_batch(x, index))
         ls, fooled, gd, _ = self.forward_backward(model, x, index, labels, True, False)
         self.update_d(gd)
         return ls, fooled

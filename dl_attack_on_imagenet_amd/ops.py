@@ -18,6 +18,7 @@ from . import _lib
 
 Tensor = torch.Tensor
 _DTYPE_CODE = {torch.float32: 0, torch.bfloat16: 1}
+ADIL_U8 = 2          # bytes u standing for u/255: the source dtype of an 8-bit image store (include/adil_hip.h)
 _workspaces = {}
 
 
@@ -265,9 +266,17 @@ def pack_codes(v, index: Optional[Tensor], batch: Optional[int] = None, pos: Opt
 def gather_images(src: Tensor, index: Optional[Tensor], out: Optional[Tensor] = None,
                   dtype: Optional[torch.dtype] = None) -> Tensor:
     """out[b] = src[index[b]] converted to `dtype` — one batch of a dataset resident in HBM (src: (R,C,H,W)).
-    index None: rows 0..B-1 of src into `out` (a pure cast, used when the dataset is uploaded)."""
+    index None: rows 0..B-1 of src into `out` (a pure cast, used when the dataset is uploaded).
+    src may be an 8-bit store (torch.uint8, byte u = u/255): it expands to float32 / bfloat16, and the float dtype must
+    be given (`dtype` or `out`) — bitwise `u.float().div(255)`, and for bf16 what the fp32 -> bf16 gather makes of that."""
     lib = _lib.load()
     _dev(src, "src")
+    if src.dtype == torch.uint8:
+        if dtype is None and out is None:
+            raise ValueError("gather_images: an 8-bit source needs an explicit float dtype (float32 or bfloat16)")
+        src_code = ADIL_U8
+    else:
+        src_code = stream_dtype_code(src.dtype)
     if index is not None:
         index = _dev(index.to(device=src.device, dtype=torch.int64), "index")
         b = index.numel()
@@ -283,9 +292,28 @@ def gather_images(src: Tensor, index: Optional[Tensor], out: Optional[Tensor] = 
         raise ValueError("gather_images: out must be (B,) + src.shape[1:] and the image size a multiple of 8")
     if index is None and b > src.shape[0]:
         raise ValueError("gather_images: more output rows than source rows")
-    _lib.check(lib.adil_gather_images(_ptr(src), stream_dtype_code(src.dtype), _ptr(index), _ptr(out),
+    _lib.check(lib.adil_gather_images(_ptr(src), src_code, _ptr(index), _ptr(out),
                                       stream_dtype_code(out.dtype), b, p, _stream()), "adil_gather_images")
     return out
+
+
+def images_to_u8(src: Tensor, out: Tensor, counter: Optional[Tensor] = None):
+    """out = rint(255 src) (bytes) for fp32 images, and the number of elements of src that are NOT 8-bit values, i.e.
+    whose fp32 bits differ from those of out/255 (adil_images_to_u8).  Returns that count as an int (one host sync), or
+    — with `counter`, a one-element int64 device tensor — adds it there and returns the counter without syncing."""
+    lib = _lib.load()
+    _dev(src, "src", torch.float32)
+    _dev(out, "out", torch.uint8)
+    if out.numel() != src.numel() or src.numel() % 8:
+        raise ValueError("images_to_u8: same number of elements, a multiple of 8")
+    own = counter is None
+    if own:
+        counter = torch.zeros(1, dtype=torch.int64, device=src.device)
+    _dev(counter, "counter", torch.int64)
+    if src.numel():
+        _lib.check(lib.adil_images_to_u8(_ptr(src), 0, _ptr(out), src.numel(), _ptr(counter), _stream()),
+                   "adil_images_to_u8")
+    return int(counter.item()) if own else counter
 
 
 def fp8_dict_supported(d: Tensor) -> bool:
@@ -346,6 +374,35 @@ def synth(x: Optional[Tensor], d: Tensor, vp: Tensor, batch: int, *, out: Option
         return out
     _lib.check(lib.adil_synth(_ptr(x), _ptr(d), _ptr(vp), _ptr(out), batch, p, k, stream_dtype_code(out.dtype),
                               float(delta_clamp), int(bool(pixel_clamp)), _stream()), "adil_synth")
+    return out
+
+
+def synth_store(store: Tensor, index: Tensor, d: Tensor, vp: Tensor, batch: int, out_dtype: torch.dtype, *,
+                out: Optional[Tensor] = None, delta_clamp: float = -1.0, pixel_clamp: bool = False) -> Tensor:
+    """out[b] = store[index[b]]/255 + vp D^T, clamps as `synth`, with x read straight out of an 8-bit image store
+    (torch.uint8, (R,C,H,W)) — no gathered copy of the batch (adil_synth_store).  float32 out is bitwise
+    synth(gather_images(store, index, dtype=float32), ...).  The fp8 contraction has no such variant."""
+    lib = _lib.load()
+    _dev(store, "store", torch.uint8)
+    _dev(d, "d", torch.float32)
+    _dev(vp, "vp", torch.float32)
+    p, k = dict_shape(d)
+    index = _dev(index.to(device=store.device, dtype=torch.int64), "index")
+    if index.numel() != batch or store.dim() < 2 or store[0].numel() != p:
+        raise ValueError("synth_store: index must hold `batch` rows of a store of images of P = C*H*W pixels")
+    if p % 8:
+        raise ValueError("synth_store: the image size must be a multiple of 8")
+    stream_dtype_code(out_dtype)
+    if out is None:
+        out = torch.empty((batch,) + tuple(store.shape[1:]), dtype=out_dtype, device=d.device)
+    _dev(out, "out", out_dtype)
+    if out.numel() != batch * p or vp.shape != (_round_up(batch, 32), _round_up(k, 16)):
+        raise ValueError("synth_store: operand shapes do not match (B, P, K)")
+    if batch == 0:
+        return out
+    _lib.check(lib.adil_synth_store(_ptr(store), _ptr(index), _ptr(d), _ptr(vp), _ptr(out), batch, p, k,
+                                    stream_dtype_code(out_dtype), float(delta_clamp), int(bool(pixel_clamp)), _stream()),
+               "adil_synth_store")
     return out
 
 

@@ -34,6 +34,7 @@ extern "C" {
 
 #define ADIL_F32 0
 #define ADIL_BF16 1
+#define ADIL_U8 2     /* bytes u, value u/255 (correctly rounded fp32): a SOURCE dtype of images only (8-bit image stores) */
 
 #define ADIL_EINVAL (-1)   /* bad argument (null pointer, non-positive size, unsupported K) */
 #define ADIL_EWORKSPACE (-2) /* workspace too small */
@@ -46,7 +47,8 @@ extern "C" {
  * adil_grad needs (`vpt`) and can take its rows from the grad_v partial sums ("slabs") of a preceding adil_grad;
  * adil_grad can leave the reduction of those slabs to its consumer (`nslabs_out`); adil_adamw_l1ball consumes them.
  * 7: adil_zstep_codes — the z-step of a DDrague iteration also produces the next iteration's codes (as slabs); the
- * persistent fp8 copy of the dictionary (adil_dict_to_fp8, adil_adamw_clamp_fp8, adil_synth_fp8_packed). */
+ * persistent fp8 copy of the dictionary (adil_dict_to_fp8, adil_adamw_clamp_fp8, adil_synth_fp8_packed).  8: 8-bit image
+ * stores — ADIL_U8 as a source of adil_gather_images, adil_images_to_u8, adil_synth_store. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -84,6 +86,14 @@ int adil_pack_codes(const float* v, const int64_t* index, int B, int K, float* v
 int adil_gather_images(const void* src, int src_dtype, const int64_t* index, void* dst, int dst_dtype, int B, int P,
                        void* stream);
 
+/* An 8-bit image store (ADIL_U8): byte u stands for the fp32 value u/255, correctly rounded — bitwise what
+ * `uint8 tensor .float().div(255)` (torchvision's ToTensor, DS_ImageNet.py:46) makes of it; bf16 destinations get that
+ * value rounded to nearest even, exactly what the fp32 -> bf16 gather makes of it.
+ * adil_images_to_u8: dst[i] = rint(255 src[i]) clamped to [0, 255], for n elements of fp32 (src_dtype ADIL_F32; n % 8 == 0,
+ * 16-byte aligned src, 8-byte aligned dst) and ADDS to *mismatches (a device counter) the number of elements whose fp32
+ * bits differ from those of dst[i]/255, i.e. the elements that are not 8-bit values (the store would change them). */
+int adil_images_to_u8(const void* src, int src_dtype, uint8_t* dst, size_t n, unsigned long long* mismatches, void* stream);
+
 /* Perturbation synthesis, fused with the add and the optional clamps:
  *     delta = vp D^T ;  delta = clamp(delta, -delta_clamp, +delta_clamp)   if delta_clamp >= 0
  *     out   = x + delta ;  out = clamp(out, 0, 1)                          if pixel_clamp
@@ -92,6 +102,13 @@ int adil_gather_images(const void* src, int src_dtype, const int64_t* index, voi
  * its +-eps clamp (adil.py:480-484) and the final [0,1] clamp (adil.py:567, :623). */
 int adil_synth(const void* x, const float* d, const float* vp, void* out, int B, int P, int K, int dtype,
                float delta_clamp, int pixel_clamp, void* stream);
+
+/* adil_synth with x read straight out of an 8-bit image store: out[b] = store[index[b]]/255 + vp D^T, same clamps, same
+ * fusion.  store is R x P bytes (R * P may exceed 4 GB: row offsets are 64-bit), index B int64 rows, out B x P in out_dtype
+ * (ADIL_F32 / ADIL_BF16).  fp32 out is bitwise adil_synth on the fp32 gather of the same rows; no gathered copy of the
+ * batch is made.  P % 8 == 0, store 4-byte aligned.  There is no fp8 variant. */
+int adil_synth_store(const uint8_t* store, const int64_t* index, const float* d, const float* vp, void* out, int B, int P,
+                     int K, int out_dtype, float delta_clamp, int pixel_clamp, void* stream);
 
 /* Precision variant of adil_synth for BASELINE.json configs[4] ("fp8 D.V MFMA on CDNA4"; no reference counterpart —
  * the reference contracts in fp32, adil.py:25): both operands of the contraction are converted to fp8 (OCP e4m3) on the
