@@ -2081,6 +2081,8 @@ __global__ __launch_bounds__(64) void grad_v_reduce_kernel(const float* __restri
 // C ABI
 // =========================================================================================================== //
 static inline int num_cu() { return adil_num_cu(); }     // 256 on MI355X (from hipDeviceAttributeMultiprocessorCount)
+static inline int imin(int a, int b) { return a < b ? a : b; }
+static inline int half_cu() { return num_cu() / 2 > 0 ? num_cu() / 2 : 1; }    // two workgroups per range, one per CU
 
 // Dynamic LDS above 48 KB has to be allowed per kernel function; asked of the runtime once per (device, function, size),
 // not on every launch.
@@ -2099,67 +2101,82 @@ static int set_lds(const void* fn, size_t bytes) {
     return 0;
 }
 
-template <int AT, int NW>
-static int launch_grad_v_f32_nw(const float* g, const float* d, float* slab, int rows, int rows_p, int P, int K, int nt, int tpw,
-                                int nwg, hipStream_t st, int k_split = 0, int nranges = 0) {
-    constexpr int TW = 32;
-    const size_t lds = (2 * 3 * (size_t)AT * 32 * (TW + DPAD) + 3 * (size_t)NW * 32 * (TW + DPAD)) * sizeof(bf16_t);
-    int rc = set_lds((const void*)grad_v_f32_kernel<AT, NW>, lds);
+// Every launch of this file: allow its LDS, launch, return the launch error.  The arguments convert to the kernel's
+// parameters; its default arguments do not apply through the pointer, so all of them are passed.
+template <typename... Params, typename... Args>
+static int launch(void (*kernel)(Params...), dim3 grid, dim3 block, size_t lds, hipStream_t st, Args... args) {
+    int rc = set_lds((const void*)kernel, lds);
     if (rc) return rc;
-    hipLaunchKernelGGL((grad_v_f32_kernel<AT, NW>), dim3(nwg), dim3(NW * 64), lds, st, g, d, slab, rows, rows_p, P, K, nt, tpw, k_split, nranges);
+    hipLaunchKernelGGL(kernel, grid, block, lds, st, args...);
     ADIL_CHECK_LAUNCH();
     return 0;
+}
+
+// Runtime values as template arguments: f(std::true_type / std::false_type), f(TypeTag<stream type>), f(integral_constant AT)
+template <typename F> static int with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
+
+template <typename T> struct TypeTag { using type = T; };
+template <typename F> static int with_dtype(int dtype, F&& f) {
+    if (dtype == ADIL_F32) return f(TypeTag<float>{});
+    if (dtype == ADIL_BF16) return f(TypeTag<bf16_t>{});
+    return ADIL_EINVAL;
 }
 
 static inline int atom_tiles(int K) { return (K + 31) / 32; }
 static inline int grad_at(int K) { const int a = atom_tiles(K); return a <= 2 ? a : 4; }       // instantiated: 1, 2, 4
+template <typename F> static int with_atom_tiles(int K, F&& f) {
+    const int at = grad_at(K);
+    if (at == 1) return f(std::integral_constant<int, 1>{});
+    if (at == 2) return f(std::integral_constant<int, 2>{});
+    return f(std::integral_constant<int, 4>{});
+}
+
+// Pixel tiles of width `tw`: [0, nfast) go through the FAST (vector-aligned) kernel when the caller's `vec` holds,
+// [nfast, ntiles) through the element-wise one.
+struct TileSplit {
+    int ntiles, nfast;
+    TileSplit(int P, int tw, bool vec) : ntiles((P + tw - 1) / tw), nfast(vec ? P / tw : 0) {}
+    int nslow() const { return ntiles - nfast; }
+};
+// n tiles over at most `slots` workgroups: tpw tiles per workgroup, nwg workgroups (none for no tiles)
+struct Spread {
+    int tpw, nwg;
+    Spread(int n, int slots) : tpw(n > 0 ? (n + slots - 1) / slots : 1), nwg(n > 0 ? (n + tpw - 1) / tpw : 0) {}
+};
+// k-split launches (two workgroups per tile range share out the atoms): 16 workgroups per 8 ranges
+static inline int k_split_grid(int nranges) { return 16 * ((nranges + 7) / 8); }
 
 // ---- K7 Gram ------------------------------------------------------------------------------------------------ //
 extern "C" size_t adil_gram_workspace_bytes(int P, int K) { (void)P; return (size_t)num_cu() * K * K * sizeof(float); }
-
-template <int AT>
-static int launch_gram(const float* d, int P, int K, float* gram, float* ws, hipStream_t st) {
-    const int nt = (P + 31) / 32, tpw = (nt + num_cu() - 1) / num_cu(), nwg = (nt + tpw - 1) / tpw;
-    const size_t lds = 2 * 3 * (size_t)AT * 32 * (32 + DPAD) * sizeof(bf16_t);
-    int rc = set_lds((const void*)gram_mfma_kernel<AT>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((gram_mfma_kernel<AT>), dim3(nwg), dim3(512), lds, st, d, ws, P, K, nt, tpw);
-    ADIL_CHECK_LAUNCH();
-    hipLaunchKernelGGL(grad_v_reduce_kernel, dim3((K * K + 63) / 64), dim3(64), 0, st, (const float*)ws, nwg, K, K, K, K, gram);
-    ADIL_CHECK_LAUNCH();
-    return 0;
-}
 
 extern "C" int adil_gram(const float* d, int P, int K, float* gram, void* ws, size_t ws_bytes, void* stream) {
     ADIL_ENTER();
     if (!d || !gram || !ws || P <= 0 || K <= 0 || K > ADIL_MAX_ATOMS) return ADIL_EINVAL;
     if (ws_bytes < adil_gram_workspace_bytes(P, K)) return ADIL_EWORKSPACE;
-    const int at = grad_at(K);
-    if (at == 1) return launch_gram<1>(d, P, K, gram, (float*)ws, (hipStream_t)stream);
-    if (at == 2) return launch_gram<2>(d, P, K, gram, (float*)ws, (hipStream_t)stream);
-    return launch_gram<4>(d, P, K, gram, (float*)ws, (hipStream_t)stream);
+    hipStream_t st = (hipStream_t)stream;
+    const int nt = (P + 31) / 32;
+    const Spread r(nt, num_cu());
+    const int rc = with_atom_tiles(K, [&](auto at) {
+        constexpr int AT = decltype(at)::value;
+        const size_t lds = 2 * 3 * (size_t)AT * 32 * (32 + DPAD) * sizeof(bf16_t);
+        return launch(gram_mfma_kernel<AT>, dim3(r.nwg), dim3(512), lds, st, d, (float*)ws, P, K, nt, r.tpw);
+    });
+    if (rc) return rc;
+    return launch(grad_v_reduce_kernel, dim3((K * K + 63) / 64), dim3(64), 0, st, (const float*)ws, r.nwg, K, K, K, K, gram);
 }
 
 // ---- K7 D M^T ----------------------------------------------------------------------------------------------- //
-template <int AT>
-static int launch_dict_rightmul(const float* d, const float* mat, int P, int K, float* out, hipStream_t st) {
-    const int Kp = round_up(K, 16), Ks = Kp + DPAD, nblocks = (P + 31) / 32;
-    const size_t lds = (3 * (size_t)AT * 32 * Ks + 2 * 3 * (size_t)32 * Ks) * sizeof(bf16_t);
-    int rc = set_lds((const void*)dict_rightmul_mfma_kernel<AT>, lds);
-    if (rc) return rc;
-    const int grid = nblocks < 4 * num_cu() ? nblocks : 4 * num_cu();
-    hipLaunchKernelGGL((dict_rightmul_mfma_kernel<AT>), dim3(grid), dim3(AT * 64), lds, st, d, mat, out, P, K, Kp, nblocks);
-    ADIL_CHECK_LAUNCH();
-    return 0;
-}
-
 extern "C" int adil_dict_rightmul(const float* d, const float* mat, int P, int K, float* out, void* stream) {
     ADIL_ENTER();
     if (!d || !mat || !out || P <= 0 || K <= 0 || K > ADIL_MAX_ATOMS) return ADIL_EINVAL;
-    const int at = grad_at(K);
-    if (at == 1) return launch_dict_rightmul<1>(d, mat, P, K, out, (hipStream_t)stream);
-    if (at == 2) return launch_dict_rightmul<2>(d, mat, P, K, out, (hipStream_t)stream);
-    return launch_dict_rightmul<4>(d, mat, P, K, out, (hipStream_t)stream);
+    const int Kp = round_up(K, 16), Ks = Kp + DPAD, nblocks = (P + 31) / 32;
+    const int grid = nblocks < 4 * num_cu() ? nblocks : 4 * num_cu();
+    return with_atom_tiles(K, [&](auto at) {
+        constexpr int AT = decltype(at)::value;
+        const size_t lds = (3 * (size_t)AT * 32 * Ks + 2 * 3 * (size_t)32 * Ks) * sizeof(bf16_t);
+        return launch(dict_rightmul_mfma_kernel<AT>, dim3(grid), dim3(AT * 64), lds, (hipStream_t)stream, d, mat, out, P, K,
+                      Kp, nblocks);
+    });
 }
 
 extern "C" size_t adil_grad_workspace_bytes(int B, int P, int K) {
@@ -2171,118 +2188,72 @@ extern "C" size_t adil_grad_workspace_bytes(int B, int P, int K) {
     return ((vpt + 255) / 256) * 256 + slab;
 }
 
-template <typename T, typename O, bool XACC, bool FAST, bool STORE = false>
+// ---- synthesis ---------------------------------------------------------------------------------------------- //
+// One tile range [tile0, tile0 + ntiles), a workgroup per tile.  STORE: x rows index[b] of the 8-bit store (xidx).
+template <typename T, typename O, bool XACC, bool FAST, bool STORE>
 static int launch_synth_range(const void* x, const float* d, const float* vp, void* out, int B, int P, int K,
-                              float delta_clamp, int pixel_clamp, int tile0, int ntiles, OpScale sc, hipStream_t st,
-                              const int64_t* xidx = nullptr) {
+                              float delta_clamp, int pixel_clamp, int tile0, int ntiles, OpScale sc, const int64_t* xidx,
+                              hipStream_t st) {
     if (ntiles <= 0) return 0;
     const int Kp = round_up(K, 16);
     const size_t lds = (size_t)DImg<O>::PLANES * SYNTH_TILE * (Kp + DPAD) * sizeof(typename DImg<O>::Elem) +
                        (STORE ? 256 * sizeof(float) : 0);     // + the byte -> value table of an 8-bit store
-    if constexpr (FAST && sizeof(typename Mma<O>::Frag) <= 16) {      // (fp32 operands: 12 registers per split fragment, 8 do not fit)
-        if (Kp > 64) {                                            // all k-groups' code fragments hoisted (see synth_sweep_buf)
-            int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, true, 8, 4, false, STORE>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, true, 8, 4, false, STORE>), dim3(ntiles), dim3(256), lds, st, (const T*)x, d, vp,
-                               (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc, xidx);
-            ADIL_CHECK_LAUNCH();
-            return 0;
+    auto run = [&](auto kernel, int nthreads) {
+        return launch(kernel, dim3(ntiles), dim3(nthreads), lds, st, (const T*)x, d, vp, (T*)out, B, P, K, Kp, delta_clamp,
+                      pixel_clamp, tile0, sc, xidx);
+    };
+    if constexpr (FAST) {
+        if (Kp > 64) {
+            // all k-groups' code fragments hoisted (see synth_sweep_buf) — but fp32 operands take 12 registers per split
+            // fragment and 8 do not fit: there 92 KB of D planes = one workgroup per CU, so 8 waves instead of 4
+            if constexpr (sizeof(typename Mma<O>::Frag) <= 16)
+                return run(synth_mfma_kernel<T, O, XACC, true, 8, 4, false, STORE>, 256);
+            else
+                return run(synth_mfma_kernel<T, O, XACC, true, 4, 8, false, STORE>, 512);
         }
     }
-    if constexpr (FAST && sizeof(typename Mma<O>::Frag) > 16) {
-        if (Kp > 64) {      // fp32 operands, K > 64: 92 KB of D planes = one workgroup per CU, so give it 8 waves instead of 4
-            int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, true, 4, 8, false, STORE>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, true, 4, 8, false, STORE>), dim3(ntiles), dim3(512), lds, st, (const T*)x, d, vp,
-                               (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc, xidx);
-            ADIL_CHECK_LAUNCH();
-            return 0;
-        }
-    }
-    int rc = set_lds((const void*)synth_mfma_kernel<T, O, XACC, FAST, 4, 4, false, STORE>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((synth_mfma_kernel<T, O, XACC, FAST, 4, 4, false, STORE>), dim3(ntiles), dim3(256), lds, st, (const T*)x, d, vp, (T*)out,
-                       B, P, K, Kp, delta_clamp, pixel_clamp, tile0, sc, xidx);
-    ADIL_CHECK_LAUNCH();
-    return 0;
+    return run(synth_mfma_kernel<T, O, XACC, FAST, 4, 4, false, STORE>, 256);
 }
 
 // full (interior, vector-aligned) tiles go through the FAST kernel, the ragged tail / unaligned rows through the
 // element-wise one
-template <typename T, typename O, bool XACC>
-static int launch_synth_x(const void* x, const float* d, const float* vp, void* out, int B, int P, int K,
-                          float delta_clamp, int pixel_clamp, OpScale sc, hipStream_t st) {
-    // FAST = vector-aligned rows, and a 32-row block addressable with 32-bit byte offsets (buffer instructions)
-    const bool vec = (P % 4 == 0) && (((uintptr_t)out | (uintptr_t)x | (uintptr_t)d) % 16 == 0) && (P <= (1 << 23));
-    const int ntiles = (P + SYNTH_TILE - 1) / SYNTH_TILE;
-    const int nfast = vec ? P / SYNTH_TILE : 0;
-    int rc = launch_synth_range<T, O, XACC, true>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, 0, nfast, sc, st);
+template <typename T, typename O, bool XACC, bool STORE = false>
+static int launch_synth_tiles(bool vec, const void* x, const float* d, const float* vp, void* out, int B, int P, int K,
+                              float delta_clamp, int pixel_clamp, OpScale sc, const int64_t* xidx, hipStream_t st) {
+    const TileSplit t(P, SYNTH_TILE, vec);
+    int rc = launch_synth_range<T, O, XACC, true, STORE>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, 0, t.nfast, sc,
+                                                         xidx, st);
     if (rc) return rc;
-    return launch_synth_range<T, O, XACC, false>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, nfast, ntiles - nfast, sc, st);
+    return launch_synth_range<T, O, XACC, false, STORE>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, t.nfast, t.nslow(),
+                                                        sc, xidx, st);
 }
 
-// adil_synth_store: the same tile split, x read out of the 8-bit store (never through buffer instructions, so only out
-// and d decide which tiles are FAST)
-template <typename T, bool XACC>
-static int launch_synth_store(const uint8_t* store, const int64_t* index, const float* d, const float* vp, void* out, int B,
-                              int P, int K, float delta_clamp, int pixel_clamp, hipStream_t st) {
-    const OpScale one{1.0f, 1.0f, 1.0f};
-    const bool vec = (((uintptr_t)out | (uintptr_t)d) % 16 == 0) && (P <= (1 << 23));
-    const int ntiles = (P + SYNTH_TILE - 1) / SYNTH_TILE;
-    const int nfast = vec ? P / SYNTH_TILE : 0;
-    int rc = launch_synth_range<T, T, XACC, true, true>(store, d, vp, out, B, P, K, delta_clamp, pixel_clamp, 0, nfast, one,
-                                                         st, index);
-    if (rc) return rc;
-    return launch_synth_range<T, T, XACC, false, true>(store, d, vp, out, B, P, K, delta_clamp, pixel_clamp, nfast,
-                                                        ntiles - nfast, one, st, index);
+// (stream dtype, x rides in the accumulator) -> f(TypeTag<T>, bool_constant<XACC>)
+template <typename F> static int with_synth_cfg(int dtype, bool xacc, F&& f) {
+    return with_dtype(dtype, [&](auto t) { return with_bool(xacc, [&](auto xa) { return f(t, xa); }); });
 }
 
-template <typename T>
-static int launch_synth(const void* x, const float* d, const float* vp, void* out, int B, int P, int K,
-                        float delta_clamp, int pixel_clamp, hipStream_t st) {
-    const bool xacc = (x != nullptr) && (delta_clamp < 0.0f);
-    const OpScale one{1.0f, 1.0f, 1.0f};
-    if (xacc) return launch_synth_x<T, T, true>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, one, st);
-    return launch_synth_x<T, T, false>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, one, st);
+// fp8 operands: codes |v| <= v_absmax -> |v sc.v| <= 384 < 448 (e4m3 max normal); dictionary |D| <= 1 (update_d clamps
+// it, adil.py:33-35)
+static OpScale fp8_scale(float v_absmax) {
+    OpScale sc;
+    sc.v = 384.0f / v_absmax;
+    sc.d = 256.0f;
+    sc.o = 1.0f / (sc.v * sc.d);
+    return sc;
 }
 
 extern "C" int adil_synth_fp8(const void* x, const float* d, const float* vp, void* out, int B, int P, int K, int dtype,
                               float v_absmax, float delta_clamp, int pixel_clamp, void* stream) {
     ADIL_ENTER();
     if (!d || !vp || !out || B <= 0 || P <= 0 || K <= 0 || K > ADIL_MAX_ATOMS || !(v_absmax > 0.0f)) return ADIL_EINVAL;
-    OpScale sc;
-    sc.v = 384.0f / v_absmax;                    // codes: |v| <= v_absmax  ->  |v sc.v| <= 384 < 448 (e4m3 max normal)
-    sc.d = 256.0f;                               // dictionary: |D| <= 1 (update_d clamps it, adil.py:33-35)
-    sc.o = 1.0f / (sc.v * sc.d);
-    hipStream_t st = (hipStream_t)stream;
+    const OpScale sc = fp8_scale(v_absmax);
+    const bool vec = (P % 4 == 0) && (((uintptr_t)out | (uintptr_t)x | (uintptr_t)d) % 16 == 0) && (P <= (1 << 23));
     const bool xacc = (x != nullptr) && (delta_clamp < 0.0f);    // x rides in the accumulator, pre-multiplied by vscale*dscale
-    if (dtype == ADIL_F32)
-        return xacc ? launch_synth_x<float, fp8_t, true>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, st)
-                    : launch_synth_x<float, fp8_t, false>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, st);
-    if (dtype == ADIL_BF16)
-        return xacc ? launch_synth_x<bf16_t, fp8_t, true>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, st)
-                    : launch_synth_x<bf16_t, fp8_t, false>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, st);
-    return ADIL_EINVAL;
-}
-
-template <typename T, bool XACC>
-static int launch_synth_fp8_packed(const void* x, const void* d8, const float* vp, void* out, int B, int P, int K,
-                                   float delta_clamp, int pixel_clamp, OpScale sc, hipStream_t st) {
-    const int Kp = round_up(K, 16), ntiles = P / SYNTH_TILE;
-    const size_t lds = (size_t)SYNTH_TILE * (Kp + DPAD);
-    if (Kp > 64) {
-        int rc = set_lds((const void*)synth_mfma_kernel<T, fp8_t, XACC, true, 8, 4, true>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((synth_mfma_kernel<T, fp8_t, XACC, true, 8, 4, true>), dim3(ntiles), dim3(256), lds, st, (const T*)x,
-                           (const float*)d8, vp, (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, 0, sc);
-    } else {
-        int rc = set_lds((const void*)synth_mfma_kernel<T, fp8_t, XACC, true, 4, 4, true>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((synth_mfma_kernel<T, fp8_t, XACC, true, 4, 4, true>), dim3(ntiles), dim3(256), lds, st, (const T*)x,
-                           (const float*)d8, vp, (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, 0, sc);
-    }
-    ADIL_CHECK_LAUNCH();
-    return 0;
+    return with_synth_cfg(dtype, xacc, [&](auto t, auto xa) {
+        return launch_synth_tiles<typename decltype(t)::type, fp8_t, decltype(xa)::value>(
+            vec, x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, nullptr, (hipStream_t)stream);
+    });
 }
 
 extern "C" int adil_synth_fp8_packed(const void* x, const void* d_fp8, const float* vp, void* out, int B, int P, int K, int dtype,
@@ -2292,28 +2263,34 @@ extern "C" int adil_synth_fp8_packed(const void* x, const void* d_fp8, const flo
     // whole 128-pixel slices of 4-byte groups, 16-byte aligned streams: everything else goes through adil_synth_fp8
     if (P % SYNTH_TILE != 0 || K % 4 != 0 || P > (1 << 23) || (((uintptr_t)out | (uintptr_t)x) % 16) != 0 || ((uintptr_t)d_fp8 % 4) != 0)
         return ADIL_EINVAL;
-    OpScale sc;
-    sc.v = 384.0f / v_absmax;
-    sc.d = 256.0f;
-    sc.o = 1.0f / (sc.v * sc.d);
-    hipStream_t st = (hipStream_t)stream;
+    const OpScale sc = fp8_scale(v_absmax);
+    const int Kp = round_up(K, 16);
+    const size_t lds = (size_t)SYNTH_TILE * (Kp + DPAD);
     const bool xacc = (x != nullptr) && (delta_clamp < 0.0f);
-    if (dtype == ADIL_F32)
-        return xacc ? launch_synth_fp8_packed<float, true>(x, d_fp8, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, st)
-                    : launch_synth_fp8_packed<float, false>(x, d_fp8, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, st);
-    if (dtype == ADIL_BF16)
-        return xacc ? launch_synth_fp8_packed<bf16_t, true>(x, d_fp8, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, st)
-                    : launch_synth_fp8_packed<bf16_t, false>(x, d_fp8, vp, out, B, P, K, delta_clamp, pixel_clamp, sc, st);
-    return ADIL_EINVAL;
+    return with_synth_cfg(dtype, xacc, [&](auto t, auto xa) {
+        using T = typename decltype(t)::type;
+        constexpr bool XACC = decltype(xa)::value;
+        auto run = [&](auto kernel) {
+            return launch(kernel, dim3(P / SYNTH_TILE), dim3(256), lds, (hipStream_t)stream, (const T*)x, (const float*)d_fp8,
+                          vp, (T*)out, B, P, K, Kp, delta_clamp, pixel_clamp, 0, sc, (const int64_t*)nullptr);
+        };
+        return Kp > 64 ? run(synth_mfma_kernel<T, fp8_t, XACC, true, 8, 4, true>)
+                       : run(synth_mfma_kernel<T, fp8_t, XACC, true, 4, 4, true>);
+    });
 }
 
 extern "C" int adil_synth(const void* x, const float* d, const float* vp, void* out, int B, int P, int K, int dtype,
                           float delta_clamp, int pixel_clamp, void* stream) {
     ADIL_ENTER();
     if (!d || !vp || !out || B <= 0 || P <= 0 || K <= 0 || K > ADIL_MAX_ATOMS) return ADIL_EINVAL;
-    if (dtype == ADIL_F32) return launch_synth<float>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, (hipStream_t)stream);
-    if (dtype == ADIL_BF16) return launch_synth<bf16_t>(x, d, vp, out, B, P, K, delta_clamp, pixel_clamp, (hipStream_t)stream);
-    return ADIL_EINVAL;
+    // FAST = vector-aligned rows, and a 32-row block addressable with 32-bit byte offsets (buffer instructions)
+    const bool vec = (P % 4 == 0) && (((uintptr_t)out | (uintptr_t)x | (uintptr_t)d) % 16 == 0) && (P <= (1 << 23));
+    const bool xacc = (x != nullptr) && (delta_clamp < 0.0f);
+    return with_synth_cfg(dtype, xacc, [&](auto t, auto xa) {
+        using T = typename decltype(t)::type;
+        return launch_synth_tiles<T, T, decltype(xa)::value>(vec, x, d, vp, out, B, P, K, delta_clamp, pixel_clamp,
+                                                              OpScale{1.0f, 1.0f, 1.0f}, nullptr, (hipStream_t)stream);
+    });
 }
 
 extern "C" int adil_synth_store(const uint8_t* store, const int64_t* index, const float* d, const float* vp, void* out, int B,
@@ -2321,77 +2298,56 @@ extern "C" int adil_synth_store(const uint8_t* store, const int64_t* index, cons
     ADIL_ENTER();
     if (!store || !index || !d || !vp || !out || B <= 0 || P <= 0 || (P & 7) || K <= 0 || K > ADIL_MAX_ATOMS) return ADIL_EINVAL;
     if ((uintptr_t)store & 3) return ADIL_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+    // the same tile split as adil_synth, x read out of the 8-bit store (never through buffer instructions, so only out
+    // and d decide which tiles are FAST)
+    const bool vec = (((uintptr_t)out | (uintptr_t)d) % 16 == 0) && (P <= (1 << 23));
     const bool xacc = delta_clamp < 0.0f;                         // as adil_synth with x present
-    if (out_dtype == ADIL_F32)
-        return xacc ? launch_synth_store<float, true>(store, index, d, vp, out, B, P, K, delta_clamp, pixel_clamp, st)
-                    : launch_synth_store<float, false>(store, index, d, vp, out, B, P, K, delta_clamp, pixel_clamp, st);
-    if (out_dtype == ADIL_BF16)
-        return xacc ? launch_synth_store<bf16_t, true>(store, index, d, vp, out, B, P, K, delta_clamp, pixel_clamp, st)
-                    : launch_synth_store<bf16_t, false>(store, index, d, vp, out, B, P, K, delta_clamp, pixel_clamp, st);
-    return ADIL_EINVAL;
+    return with_synth_cfg(out_dtype, xacc, [&](auto t, auto xa) {
+        using T = typename decltype(t)::type;
+        return launch_synth_tiles<T, T, decltype(xa)::value, true>(vec, store, d, vp, out, B, P, K, delta_clamp, pixel_clamp,
+                                                                    OpScale{1.0f, 1.0f, 1.0f}, index, (hipStream_t)stream);
+    });
 }
 
-static inline int imin(int a, int b) { return a < b ? a : b; }
-
-// What the caller of adil_grad brings along / takes over (ABI 6).
-struct GradOpts {
-    const void* vpt_in;   // codes already transposed [KA][Bp] in the MFMA element type of the stream (adil_pack_codes), or null
+// ---- grad ------------------------------------------------------------------------------------------------------ //
+// adil_grad's operands.  The slabs (grad_v partial sums, one per workgroup) follow the transposed codes in the workspace.
+template <typename T> struct Grad {
+    using E = typename Mma<T>::Elem;
+    const T* g;
+    const float* d;
+    float* grad_d;
+    float* grad_vb;
+    int B, Bp, P, K, accumulate_d;
+    const E* vpt;         // vpt[a][b] = vp[b][a], KA x Bp (grad_d)
+    float* slab;
     int* nslabs_out;      // non-null: the caller reduces the grad_v slabs itself (adil_adamw_l1ball / adil_pack_codes) when
                           // ONE row chunk covers the batch; receives the slab count, 0 = reduced here into grad_vb as usual
+    hipStream_t st;
+    // FAST tiles at all: rows of a multiple of `p_multiple` pixels (each route has its own) on a 16-byte aligned g
+    bool vec(int p_multiple) const { return P % p_multiple == 0 && (uintptr_t)g % 16 == 0; }
 };
 
-// vpt[a][b] = vp[b][a] in the element type E: supplied by the caller, or made here (one small launch)
-template <typename E>
-static int transposed_codes(const float* vp, const GradOpts& o, void* ws, int Bp, int Kp, int KA, hipStream_t st, const E** out) {
-    if (o.vpt_in != nullptr) { *out = reinterpret_cast<const E*>(o.vpt_in); return 0; }
-    E* vpt = reinterpret_cast<E*>(ws);
-    hipLaunchKernelGGL((transpose_codes_kernel<E>), dim3((KA * Bp + 255) / 256), dim3(256), 0, st, vp, Bp, Kp, KA, vpt);
-    ADIL_CHECK_LAUNCH();
-    *out = vpt;
+// Row chunks of `chunk` rows, the last one ragged: run(r0, rows, rows_p, acc_d) launches one chunk's kernels; grad_d
+// accumulates from the second chunk on.  The `nslabs` grad_v slabs a chunk leaves (0: grad_d only) then go to the
+// caller (one chunk covers the batch) or are reduced here into the chunk's rows of grad_vb (slab rows are K wide).
+template <typename T, typename F>
+static int for_row_chunks(const Grad<T>& a, int chunk, int nslabs, F&& run) {
+    for (int r0 = 0; r0 < a.Bp; r0 += chunk) {
+        const int rows_p = imin(a.Bp - r0, chunk), rows = imin(a.B - r0, rows_p);
+        int rc = run(r0, rows, rows_p, a.accumulate_d || r0 > 0);
+        if (rc == 0 && nslabs > 0) {
+            if (a.nslabs_out != nullptr && a.Bp <= chunk) *a.nslabs_out = nslabs;
+            else rc = launch(grad_v_reduce_kernel, dim3((rows_p * a.K + 63) / 64), dim3(64), 0, a.st, (const float*)a.slab,
+                             nslabs, rows_p, a.K, rows, a.K, a.grad_vb + (size_t)r0 * a.K);
+        }
+        if (rc) return rc;
+    }
     return 0;
 }
 
-// after a row chunk's kernels wrote `nslabs` slabs: hand them to the caller (single chunk) or reduce them here
-static int finish_slabs(const float* slab, int nslabs, int rows, int rows_p, int K, float* grad_vb_rows, bool single_chunk,
-                        const GradOpts& o, hipStream_t st) {
-    if (o.nslabs_out != nullptr && single_chunk) { *o.nslabs_out = nslabs; return 0; }
-    hipLaunchKernelGGL(grad_v_reduce_kernel, dim3((rows_p * K + 63) / 64), dim3(64), 0, st, slab, nslabs, rows_p, K, rows, K,
-                       grad_vb_rows);
-    ADIL_CHECK_LAUNCH();
-    return 0;
-}
+// rows per fused launch, bounded by LDS (one image per 32 rows + partials); the fused pass runs for K <= 64 only
+template <typename T> struct FusedCfg { static constexpr int kMaxRows = sizeof(T) == 2 ? 512 : 256; };
 
-template <typename T, int PXT, int AT, bool FAST>
-static int launch_grad_d_range(const T* g, const typename Mma<T>::Elem* vpt, int vstride, float* grad_d, int B, int Bp,
-                               int P, int K, int acc_d, int tile_begin, int tile_end, hipStream_t st) {
-    const int n = tile_end - tile_begin;
-    if (n <= 0) return 0;
-    hipLaunchKernelGGL((grad_d_mfma_kernel<T, PXT, AT, FAST>), dim3((n + 3) / 4), dim3(256), 0, st, g, vpt, vstride, grad_d,
-                       B, Bp, P, K, acc_d, tile_begin, tile_end);
-    ADIL_CHECK_LAUNCH();
-    return 0;
-}
-
-template <typename T, int PXT, int AT>
-static int launch_grad_d(const T* g, const float* vp, float* grad_d, int B, int P, int K, int accumulate_d, void* ws,
-                         const GradOpts& o, hipStream_t st) {
-    using E = typename Mma<T>::Elem;
-    constexpr int KA = AT * 32;
-    constexpr int TW = PXT * 32;
-    const int Kp = round_up(K, 16), Bp = round_up(B, 32);
-    const E* vpt;
-    int rc = transposed_codes<E>(vp, o, ws, Bp, Kp, KA, st, &vpt);
-    if (rc) return rc;
-    const int ntiles = (P + TW - 1) / TW;
-    const bool vec = (P % 4 == 0) && ((uintptr_t)g % 16 == 0);
-    const int nfast = vec ? P / TW : 0;
-    rc = launch_grad_d_range<T, PXT, AT, true>(g, vpt, Bp, grad_d, B, Bp, P, K, accumulate_d, 0, nfast, st);
-    if (rc) return rc;
-    return launch_grad_d_range<T, PXT, AT, false>(g, vpt, Bp, grad_d, B, Bp, P, K, accumulate_d, nfast, ntiles, st);
-}
-
-// waves (= 32-row batch blocks) per grad_v workgroup: bounded by the 160 KiB of LDS holding one g image per wave
 // waves (= 32-row blocks) per grad_v workgroup, bounded by LDS: fp32 streams stage three planes of the D tile
 template <typename T, int AT> struct GradVWaves { static constexpr int kMax = sizeof(T) == 2 ? 16 : (AT <= 2 ? 8 : 4); };
 
@@ -2402,399 +2358,204 @@ static size_t grad_v_lds_bytes(int nwaves) {
     return 2 * (size_t)DImg<T>::PLANES * AT * 32 * GD * sizeof(bf16_t) + (size_t)nwaves * 32 * GS * sizeof(E);
 }
 
-template <typename T, int AT, int NW, bool FAST>
-static int launch_grad_v_nw(const T* g, const float* d, float* slab, int rows, int rows_p, int P, int K, int tile_begin,
-                            int tile_end, int nwg, int tiles_per_wg, hipStream_t st) {
-    const size_t lds = grad_v_lds_bytes<T, AT>(NW);
-    int rc = set_lds((const void*)grad_v_mfma_kernel<T, AT, NW, FAST>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((grad_v_mfma_kernel<T, AT, NW, FAST>), dim3(nwg), dim3(NW * 64), lds, st, g, d, slab, rows, rows_p, P,
-                       K, tile_begin, tile_end, tiles_per_wg);
-    ADIL_CHECK_LAUNCH();
-    return 0;
-}
-
-template <typename T, int AT, bool FAST>
-static int launch_grad_v_range(const T* g, const float* d, float* slab, int rows, int rows_p, int P, int K, int tile_begin,
-                               int tile_end, int nwg, int tiles_per_wg, hipStream_t st) {
-    if (nwg <= 0) return 0;
-    const int nwaves = rows_p / 32;                               // <= GradVWaves<T, AT>::kMax
-    if constexpr (GradVWaves<T, AT>::kMax >= 16) {
-        if (nwaves > 8) return launch_grad_v_nw<T, AT, 16, FAST>(g, d, slab, rows, rows_p, P, K, tile_begin, tile_end, nwg, tiles_per_wg, st);
-    }
-    if constexpr (GradVWaves<T, AT>::kMax >= 8) {
-        if (nwaves > 4) return launch_grad_v_nw<T, AT, 8, FAST>(g, d, slab, rows, rows_p, P, K, tile_begin, tile_end, nwg, tiles_per_wg, st);
-    }
-    return launch_grad_v_nw<T, AT, 4, FAST>(g, d, slab, rows, rows_p, P, K, tile_begin, tile_end, nwg, tiles_per_wg, st);
-}
-
-template <typename T, int AT>
-static int launch_grad_v(const T* g, const float* d, float* grad_vb, int B, int P, int K, float* slab, const GradOpts& o,
-                         hipStream_t st) {
-    constexpr int KA = AT * 32;
-    const int Bp = round_up(B, 32);
-    const int ntiles = (P + GV_TW - 1) / GV_TW;
-    const bool vec = (P % 8 == 0) && ((uintptr_t)g % 16 == 0);
-    const int nfast = vec ? P / GV_TW : 0, nslow = ntiles - nfast;
-    const int tpw_fast = nfast > 0 ? (nfast + num_cu() - 1) / num_cu() : 1;
-    const int nwg_fast = nfast > 0 ? (nfast + tpw_fast - 1) / tpw_fast : 0;
-    const int tpw_slow = nslow > 0 ? (nslow + num_cu() - 1) / num_cu() : 1;
-    const int nwg_slow = nslow > 0 ? (nslow + tpw_slow - 1) / tpw_slow : 0;
-    if constexpr (sizeof(T) == 4) {
-        if (vec && P % 32 == 0) {             // fp32 streams: planes split once; 512 rows per launch (K > 64: 256, the D planes double)
-            if constexpr (AT == 4) {
-                // K > 64 (round 4): the AT = 2 shape, 512 rows per launch, the atoms split over workgroup pairs — D read
-                // once, ONE slab per range, so a 512-row batch needs neither a second launch nor a reduce launch
-                const int kh = (K + 1) / 2, half_cu = num_cu() / 2 > 0 ? num_cu() / 2 : 1;
-                const int nt = P / 32, tpw = (nt + half_cu - 1) / half_cu, nr = (nt + tpw - 1) / tpw, grid = 16 * ((nr + 7) / 8);
-                for (int r0 = 0; r0 < Bp; r0 += 512) {
-                    const int rows_p = imin(Bp - r0, 512), rows = imin(B - r0, rows_p);
-                    const float* gc = (const float*)g + (size_t)r0 * P;
-                    int rc;
-                    if (rows_p > 256) rc = launch_grad_v_f32_nw<2, 16>(gc, d, slab, rows, rows_p, P, K, nt, tpw, grid, st, kh, nr);
-                    else if (rows_p > 128) rc = launch_grad_v_f32_nw<2, 8>(gc, d, slab, rows, rows_p, P, K, nt, tpw, grid, st, kh, nr);
-                    else rc = launch_grad_v_f32_nw<2, 4>(gc, d, slab, rows, rows_p, P, K, nt, tpw, grid, st, kh, nr);
-                    if (rc) return rc;
-                    rc = finish_slabs(slab, nr, rows, rows_p, K, grad_vb + (size_t)r0 * K, Bp <= 512, o, st);
-                    if (rc) return rc;
-                }
-                return 0;
-            }
-            constexpr int kRows = AT <= 2 ? 512 : 256;
-            const int nt = P / 32, tpw = (nt + num_cu() - 1) / num_cu(), nwg = (nt + tpw - 1) / tpw;
-            for (int r0 = 0; r0 < Bp; r0 += kRows) {
-                const int rows_p = imin(Bp - r0, kRows), rows = imin(B - r0, rows_p);
-                const float* gc = (const float*)g + (size_t)r0 * P;
-                int rc;
-                if constexpr (AT <= 2) {
-                    if (rows_p > 256) rc = launch_grad_v_f32_nw<AT, 16>(gc, d, slab, rows, rows_p, P, K, nt, tpw, nwg, st);
-                    else if (rows_p > 128) rc = launch_grad_v_f32_nw<AT, 8>(gc, d, slab, rows, rows_p, P, K, nt, tpw, nwg, st);
-                    else rc = launch_grad_v_f32_nw<AT, 4>(gc, d, slab, rows, rows_p, P, K, nt, tpw, nwg, st);
-                } else {
-                    if (rows_p > 128) rc = launch_grad_v_f32_nw<AT, 8>(gc, d, slab, rows, rows_p, P, K, nt, tpw, nwg, st);
-                    else rc = launch_grad_v_f32_nw<AT, 4>(gc, d, slab, rows, rows_p, P, K, nt, tpw, nwg, st);
-                }
-                if (rc) return rc;
-                rc = finish_slabs(slab, nwg, rows, rows_p, K, grad_vb + (size_t)r0 * K, Bp <= kRows, o, st);
-                if (rc) return rc;
-            }
-            return 0;
-        }
-    }
-    const int chunk = GradVWaves<T, AT>::kMax * 32;
-    for (int r0 = 0; r0 < Bp; r0 += chunk) {
-        const int rows_p = imin(Bp - r0, chunk), rows = imin(B - r0, rows_p);
-        const T* gc = g + (size_t)r0 * P;
-        int rc = launch_grad_v_range<T, AT, true>(gc, d, slab, rows, rows_p, P, K, 0, nfast, nwg_fast, tpw_fast, st);
-        if (rc) return rc;
-        rc = launch_grad_v_range<T, AT, false>(gc, d, slab + (size_t)nwg_fast * rows_p * K, rows, rows_p, P, K, nfast,
-                                               ntiles, nwg_slow, tpw_slow, st);
-        if (rc) return rc;
-        rc = finish_slabs(slab, nwg_fast + nwg_slow, rows, rows_p, K, grad_vb + (size_t)r0 * K, Bp <= chunk, o, st);   // slab rows are K wide
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// ---- fused single-pass grad (both outputs) ------------------------------------------------------------------ //
-template <typename T, int AT> struct FusedCfg {
-    // rows per workgroup launch, bounded by LDS (one image per 32 rows + partials); 0 = not available
-    static constexpr int kMaxRows = (sizeof(T) == 2) ? (AT <= 2 ? 512 : 256) : (AT <= 2 ? 256 : 0);
-};
-
-template <typename T, int AT, int NW, int RB>
+// WV = false: grad_d alone, no D planes
+template <typename T, int AT, int NW, int RB, bool WV = true>
 static size_t grad_fused_lds_bytes() {
     using E = typename Mma<T>::Elem;
     const size_t GS = GV_TW + Mma<T>::PAD, GD = GV_TW + DPAD;
-    return 2 * (size_t)DImg<T>::PLANES * AT * 32 * GD * sizeof(bf16_t) + (size_t)NW * RB * 32 * GS * sizeof(E) +
+    return (WV ? 2 * (size_t)DImg<T>::PLANES * AT * 32 * GD * sizeof(bf16_t) : 0) + (size_t)NW * RB * 32 * GS * sizeof(E) +
            (size_t)NW * 16 * 64 * sizeof(float);
 }
 
-template <typename T, int AT, int NW, int RB, bool FAST>
-static int launch_grad_fused_nw(const T* g, const float* d, const typename Mma<T>::Elem* vpt, int vstride, float* grad_d,
-                                float* slab, int rows, int rows_p, int P, int K, int acc_d, int tile_begin, int tile_end,
-                                int nwg, int tiles_per_wg, hipStream_t st, int k_split = 0, int nranges = 0) {
-    if constexpr (NW % (2 * AT) != 0) {
-        return ADIL_EINVAL;
-    } else {
-        const size_t lds = grad_fused_lds_bytes<T, AT, NW, RB>();
-        if (acc_d) {
-            int rc = set_lds((const void*)grad_fused_mfma_kernel<T, AT, NW, RB, FAST, true>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((grad_fused_mfma_kernel<T, AT, NW, RB, FAST, true>), dim3(nwg), dim3(NW * 64), lds, st, g, d,
-                               vpt, vstride, grad_d, slab, rows, rows_p, P, K, tile_begin, tile_end, tiles_per_wg, k_split, nranges);
-        } else {
-            int rc = set_lds((const void*)grad_fused_mfma_kernel<T, AT, NW, RB, FAST, false>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((grad_fused_mfma_kernel<T, AT, NW, RB, FAST, false>), dim3(nwg), dim3(NW * 64), lds, st, g, d,
-                               vpt, vstride, grad_d, slab, rows, rows_p, P, K, tile_begin, tile_end, tiles_per_wg, k_split, nranges);
-        }
-        ADIL_CHECK_LAUNCH();
-        return 0;
-    }
+// One row chunk of grad_fused_mfma_kernel: the FAST tiles on ranges f, then the slow tail on ranges s, whose slabs follow
+// the fast ones.  k_split > 0: two workgroups per range, [0, k_split) and [k_split, K) of the atoms.
+template <typename T, int AT, int NW, int RB, bool WV = true>
+static int launch_grad_fused_chunk(const Grad<T>& a, int r0, int rows, int rows_p, bool acc_d, const TileSplit& t,
+                                   const Spread& f, const Spread& s, int k_split = 0) {
+    auto run = [&](auto kernel, float* slab, int t0, int t1, const Spread& r) {
+        if (r.nwg <= 0) return 0;
+        return launch(kernel, dim3(k_split > 0 ? k_split_grid(r.nwg) : r.nwg), dim3(NW * 64),
+                      grad_fused_lds_bytes<T, AT, NW, RB, WV>(), a.st, a.g + (size_t)r0 * a.P, WV ? a.d : nullptr, a.vpt + r0, a.Bp, a.grad_d, slab, rows, rows_p, a.P,
+                      a.K, t0, t1, r.tpw, k_split, k_split > 0 ? r.nwg : 0);
+    };
+    return with_bool(acc_d, [&](auto acc) {
+        constexpr bool ACC = decltype(acc)::value;
+        int rc = run(grad_fused_mfma_kernel<T, AT, NW, RB, true, ACC, WV>, WV ? a.slab : nullptr, 0, t.nfast, f);
+        if (rc) return rc;
+        return run(grad_fused_mfma_kernel<T, AT, NW, RB, false, ACC, WV>, WV ? a.slab + (size_t)f.nwg * rows_p * a.K : nullptr,
+                   t.nfast, t.ntiles, s);
+    });
 }
 
-template <typename T, int AT, bool FAST>
-static int launch_grad_fused_range(const T* g, const float* d, const typename Mma<T>::Elem* vpt, int vstride,
-                                   float* grad_d, float* slab, int rows, int rows_p, int P, int K, int acc_d,
-                                   int tile_begin, int tile_end, int nwg, int tiles_per_wg, hipStream_t st) {
-    if (nwg <= 0) return 0;
-    const int nblk = rows_p / 32;
-    if constexpr (FusedCfg<T, AT>::kMaxRows >= 512) {
-        if (nblk > 8) return launch_grad_fused_nw<T, AT, 8, 2, FAST>(g, d, vpt, vstride, grad_d, slab, rows, rows_p, P, K, acc_d, tile_begin, tile_end, nwg, tiles_per_wg, st);
-    }
-    if (nblk > 4 || 4 % (2 * AT) != 0)
-        return launch_grad_fused_nw<T, AT, 8, 1, FAST>(g, d, vpt, vstride, grad_d, slab, rows, rows_p, P, K, acc_d, tile_begin, tile_end, nwg, tiles_per_wg, st);
-    return launch_grad_fused_nw<T, AT, 4, 1, FAST>(g, d, vpt, vstride, grad_d, slab, rows, rows_p, P, K, acc_d, tile_begin, tile_end, nwg, tiles_per_wg, st);
-}
-
-template <typename T, int AT>
-static int launch_grad_fused(const T* g, const float* d, const float* vp, float* grad_d, float* grad_vb, int B, int P,
-                             int K, int accumulate_d, void* ws, float* slab, const GradOpts& o, hipStream_t st) {
-    using E = typename Mma<T>::Elem;
-    constexpr int KA = AT * 32;
-    const int Kp = round_up(K, 16), Bp = round_up(B, 32);
-    const E* vpt;
-    {
-        int rc = transposed_codes<E>(vp, o, ws, Bp, Kp, KA, st, &vpt);
-        if (rc) return rc;
-    }
-    const int ntiles = (P + GV_TW - 1) / GV_TW;
-    const bool vec = (P % 8 == 0) && ((uintptr_t)g % 16 == 0);
-    const int nfast = vec ? P / GV_TW : 0, nslow = ntiles - nfast;
-    const int tpw_fast = nfast > 0 ? (nfast + num_cu() - 1) / num_cu() : 1;
-    const int nwg_fast = nfast > 0 ? (nfast + tpw_fast - 1) / tpw_fast : 0;
-    const int tpw_slow = nslow > 0 ? (nslow + num_cu() - 1) / num_cu() : 1;
-    const int nwg_slow = nslow > 0 ? (nslow + tpw_slow - 1) / tpw_slow : 0;
-    const int chunk = FusedCfg<T, AT>::kMaxRows;
-    if constexpr (sizeof(T) == 4 && AT <= 2) {
-        // fp32 streams, aligned rows, whole 32-pixel tiles: every operand split once (grad_fused_f32_kernel)
-        if (vec && P % 32 == 0) {
-            constexpr int NW = 8, TW = 32;
-            const int nt = P / TW, tpw = (nt + num_cu() - 1) / num_cu(), nwg = (nt + tpw - 1) / tpw;
-            const size_t lds = (2 * 3 * (size_t)KA * (TW + DPAD) + 3 * (size_t)NW * 32 * (TW + DPAD)) * sizeof(bf16_t) +
-                               (size_t)NW * 16 * 64 * sizeof(float);
-            int rc = set_lds((const void*)grad_fused_f32_kernel<AT, NW, false>, lds);
-            if (rc) return rc;
-            rc = set_lds((const void*)grad_fused_f32_kernel<AT, NW, true>, lds);
-            if (rc) return rc;
-            for (int r0 = 0; r0 < Bp; r0 += NW * 32) {
-                const int rows_p = imin(Bp - r0, NW * 32), rows = imin(B - r0, rows_p);
-                const float* gc = (const float*)g + (size_t)r0 * P;
-                if (accumulate_d || r0 > 0)
-                    hipLaunchKernelGGL((grad_fused_f32_kernel<AT, NW, true>), dim3(nwg), dim3(NW * 64), lds, st, gc, d,
-                                       (const float*)vpt + r0, Bp, grad_d, slab, rows, rows_p, P, K, nt, tpw);
-                else
-                    hipLaunchKernelGGL((grad_fused_f32_kernel<AT, NW, false>), dim3(nwg), dim3(NW * 64), lds, st, gc, d,
-                                       (const float*)vpt + r0, Bp, grad_d, slab, rows, rows_p, P, K, nt, tpw);
-                ADIL_CHECK_LAUNCH();
-                rc = finish_slabs(slab, nwg, rows, rows_p, K, grad_vb + (size_t)r0 * K, Bp <= NW * 32, o, st);
-                if (rc) return rc;
-            }
-            return 0;
-        }
-    }
-    for (int r0 = 0; r0 < Bp; r0 += chunk) {
-        const int rows_p = imin(Bp - r0, chunk), rows = imin(B - r0, rows_p);
-        const T* gc = g + (size_t)r0 * P;
-        const int acc_d = accumulate_d || (r0 > 0);
-        int rc = launch_grad_fused_range<T, AT, true>(gc, d, vpt + r0, Bp, grad_d, slab, rows, rows_p, P, K, acc_d, 0, nfast,
-                                                      nwg_fast, tpw_fast, st);
-        if (rc) return rc;
-        rc = launch_grad_fused_range<T, AT, false>(gc, d, vpt + r0, Bp, grad_d, slab + (size_t)nwg_fast * rows_p * K, rows,
-                                                   rows_p, P, K, acc_d, nfast, ntiles, nwg_slow, tpw_slow, st);
-        if (rc) return rc;
-        rc = finish_slabs(slab, nwg_fast + nwg_slow, rows, rows_p, K, grad_vb + (size_t)r0 * K, Bp <= chunk, o, st);   // slab rows are K wide
-        if (rc) return rc;
-    }
-    return 0;
-}
-
-// ---- fused single pass for 64 < K <= 128 on bf16 streams: two workgroups per tile range split the ATOMS ---------------- //
+// ---- both outputs, 64 < K <= 128 on bf16 streams: two workgroups per tile range split the ATOMS ------------------- //
 // (see grad_fused_mfma_kernel, k_split).  The K <= 64 instantiations (AT = 2 tiles, 8 waves x 2 row blocks = 512 rows) do
 // the work; each half owns ceil(K/2) / floor(K/2) atoms.  One launch per 512-row chunk; later chunks accumulate into grad_d.
 template <typename T>
-static int launch_grad_fused_split(const T* g, const float* d, const float* vp, float* grad_d, float* grad_vb, int B, int P,
-                                   int K, int accumulate_d, void* ws, float* slab, const GradOpts& o, hipStream_t st) {
-    using E = typename Mma<T>::Elem;
-    constexpr int AT = 2;
-    const int Kp = round_up(K, 16), Bp = round_up(B, 32), KA = grad_at(K) * 32;
-    const E* vpt;
-    {
-        int rc = transposed_codes<E>(vp, o, ws, Bp, Kp, KA, st, &vpt);
-        if (rc) return rc;
-    }
-    const int kh = (K + 1) / 2;                                   // atoms of the first half; both halves <= 64
-    const int ntiles = (P + GV_TW - 1) / GV_TW;
-    const bool vec = (P % 8 == 0) && ((uintptr_t)g % 16 == 0);
-    const int nfast = vec ? P / GV_TW : 0, nslow = ntiles - nfast;
-    const int half_cu = num_cu() / 2 > 0 ? num_cu() / 2 : 1;     // two workgroups per range, one workgroup per CU
-    const int tpw_fast = nfast > 0 ? (nfast + half_cu - 1) / half_cu : 1, nr_fast = nfast > 0 ? (nfast + tpw_fast - 1) / tpw_fast : 0;
-    const int tpw_slow = nslow > 0 ? (nslow + half_cu - 1) / half_cu : 1, nr_slow = nslow > 0 ? (nslow + tpw_slow - 1) / tpw_slow : 0;
-    for (int r0 = 0; r0 < Bp; r0 += 512) {
-        const int rows_p = imin(Bp - r0, 512), rows = imin(B - r0, rows_p);
-        const T* gc = g + (size_t)r0 * P;
-        const int acc_d = accumulate_d || (r0 > 0);
-        int rc = 0;
-        if (nr_fast > 0) {
-            const int grid = 16 * ((nr_fast + 7) / 8);
-            if (rows_p > 256) rc = launch_grad_fused_nw<T, AT, 8, 2, true>(gc, d, vpt + r0, Bp, grad_d, slab, rows, rows_p, P, K, acc_d, 0, nfast, grid, tpw_fast, st, kh, nr_fast);
-            else rc = launch_grad_fused_nw<T, AT, 8, 1, true>(gc, d, vpt + r0, Bp, grad_d, slab, rows, rows_p, P, K, acc_d, 0, nfast, grid, tpw_fast, st, kh, nr_fast);
-            if (rc) return rc;
+static int launch_grad_fused_split(const Grad<T>& a) {
+    const int kh = (a.K + 1) / 2;                                 // atoms of the first half; both halves <= 64
+    const TileSplit t(a.P, GV_TW, a.vec(8));
+    const Spread f(t.nfast, half_cu()), s(t.nslow(), half_cu());
+    return for_row_chunks(a, 512, f.nwg + s.nwg, [&](int r0, int rows, int rows_p, bool acc_d) {
+        if (rows_p > 256) return launch_grad_fused_chunk<T, 2, 8, 2>(a, r0, rows, rows_p, acc_d, t, f, s, kh);
+        return launch_grad_fused_chunk<T, 2, 8, 1>(a, r0, rows, rows_p, acc_d, t, f, s, kh);
+    });
+}
+
+// ---- both outputs, K <= 64: the generic fused pass, NW x RB row blocks from the chunk ------------------------------ //
+template <typename T, int AT>
+static int launch_grad_fused(const Grad<T>& a) {
+    const TileSplit t(a.P, GV_TW, a.vec(8));
+    const Spread f(t.nfast, num_cu()), s(t.nslow(), num_cu());
+    return for_row_chunks(a, FusedCfg<T>::kMaxRows, f.nwg + s.nwg, [&](int r0, int rows, int rows_p, bool acc_d) {
+        const int nblk = rows_p / 32;
+        if constexpr (FusedCfg<T>::kMaxRows >= 512) {
+            if (nblk > 8) return launch_grad_fused_chunk<T, AT, 8, 2>(a, r0, rows, rows_p, acc_d, t, f, s);
         }
-        if (nr_slow > 0) {
-            const int grid = 16 * ((nr_slow + 7) / 8);
-            float* sl = slab + (size_t)nr_fast * rows_p * K;
-            if (rows_p > 256) rc = launch_grad_fused_nw<T, AT, 8, 2, false>(gc, d, vpt + r0, Bp, grad_d, sl, rows, rows_p, P, K, acc_d, nfast, ntiles, grid, tpw_slow, st, kh, nr_slow);
-            else rc = launch_grad_fused_nw<T, AT, 8, 1, false>(gc, d, vpt + r0, Bp, grad_d, sl, rows, rows_p, P, K, acc_d, nfast, ntiles, grid, tpw_slow, st, kh, nr_slow);
-            if (rc) return rc;
-        }
-        rc = finish_slabs(slab, nr_fast + nr_slow, rows, rows_p, K, grad_vb + (size_t)r0 * K, Bp <= 512, o, st);
-        if (rc) return rc;
-    }
-    return 0;
+        if (nblk > 4) return launch_grad_fused_chunk<T, AT, 8, 1>(a, r0, rows, rows_p, acc_d, t, f, s);
+        return launch_grad_fused_chunk<T, AT, 4, 1>(a, r0, rows, rows_p, acc_d, t, f, s);
+    });
+}
+
+// ---- fp32 streams, aligned rows, whole 32-pixel tiles: grad_fused_f32_kernel, every operand split once, 256 rows per
+// launch.  WV = false: its grad_d half alone (K > 64, pre-split operands).
+template <int AT, bool WV>
+static int launch_grad_fused_f32(const Grad<float>& a) {
+    constexpr int NW = 8, TW = 32;
+    const int nt = a.P / TW;
+    const Spread r(nt, num_cu());
+    const size_t lds = ((WV ? 2 * 3 * (size_t)AT * 32 * (TW + DPAD) : 0) + 3 * (size_t)NW * 32 * (TW + DPAD)) * sizeof(bf16_t) +
+                       (size_t)NW * 16 * 64 * sizeof(float);
+    return for_row_chunks(a, NW * 32, WV ? r.nwg : 0, [&](int r0, int rows, int rows_p, bool acc_d) {
+        return with_bool(acc_d, [&](auto acc) {
+            return launch(grad_fused_f32_kernel<AT, NW, decltype(acc)::value, WV>, dim3(r.nwg), dim3(NW * 64), lds, a.st,
+                          a.g + (size_t)r0 * a.P, WV ? a.d : nullptr, a.vpt + r0, a.Bp, a.grad_d, WV ? a.slab : nullptr, rows,
+                          rows_p, a.P, a.K, nt, r.tpw);
+        });
+    });
 }
 
 // ---- grad_d alone through LDS (K > 64, bf16 streams): the grad_d half of the fused kernel, 512 rows per launch -------- //
-template <typename T, int AT, int NW, int RB, bool FAST>
-static int launch_grad_d_lds_nw(const T* g, const typename Mma<T>::Elem* vpt, int vstride, float* grad_d, int rows, int rows_p,
-                                int P, int K, int acc_d, int tile_begin, int tile_end, int nwg, int tpw, hipStream_t st) {
-    using E = typename Mma<T>::Elem;
-    if (nwg <= 0) return 0;
-    const size_t lds = (size_t)NW * RB * 32 * (GV_TW + Mma<T>::PAD) * sizeof(E) + (size_t)NW * 16 * 64 * sizeof(float);
-    if (acc_d) {
-        int rc = set_lds((const void*)grad_fused_mfma_kernel<T, AT, NW, RB, FAST, true, false>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((grad_fused_mfma_kernel<T, AT, NW, RB, FAST, true, false>), dim3(nwg), dim3(NW * 64), lds, st, g,
-                           (const float*)nullptr, vpt, vstride, grad_d, (float*)nullptr, rows, rows_p, P, K, tile_begin, tile_end, tpw, 0, 0);
-    } else {
-        int rc = set_lds((const void*)grad_fused_mfma_kernel<T, AT, NW, RB, FAST, false, false>, lds);
-        if (rc) return rc;
-        hipLaunchKernelGGL((grad_fused_mfma_kernel<T, AT, NW, RB, FAST, false, false>), dim3(nwg), dim3(NW * 64), lds, st, g,
-                           (const float*)nullptr, vpt, vstride, grad_d, (float*)nullptr, rows, rows_p, P, K, tile_begin, tile_end, tpw, 0, 0);
-    }
-    ADIL_CHECK_LAUNCH();
-    return 0;
+template <typename T>
+static int launch_grad_d_lds(const Grad<T>& a) {
+    const TileSplit t(a.P, GV_TW, a.vec(8));
+    const Spread f(t.nfast, num_cu()), s(t.nslow(), num_cu());
+    return for_row_chunks(a, 512, 0, [&](int r0, int rows, int rows_p, bool acc_d) {
+        if (rows_p > 256) return launch_grad_fused_chunk<T, 4, 8, 2, false>(a, r0, rows, rows_p, acc_d, t, f, s);
+        return launch_grad_fused_chunk<T, 4, 8, 1, false>(a, r0, rows, rows_p, acc_d, t, f, s);
+    });
+}
+
+// ---- grad_d alone, direct loads: grad_d_mfma_kernel, all rows per launch ------------------------------------------- //
+template <typename T, int AT>
+static int launch_grad_d(const Grad<T>& a) {
+    constexpr int PXT = AT == 1 ? 4 : 2;                          // 32-pixel blocks per tile
+    const TileSplit t(a.P, PXT * 32, a.vec(4));
+    auto run = [&](auto kernel, int t0, int t1) {
+        if (t1 <= t0) return 0;
+        return launch(kernel, dim3((t1 - t0 + 3) / 4), dim3(256), 0, a.st, a.g, a.vpt, a.Bp, a.grad_d, a.B, a.Bp, a.P, a.K,
+                      a.accumulate_d, t0, t1);
+    };
+    int rc = run(grad_d_mfma_kernel<T, PXT, AT, true>, 0, t.nfast);
+    if (rc) return rc;
+    return run(grad_d_mfma_kernel<T, PXT, AT, false>, t.nfast, t.ntiles);
+}
+
+// ---- grad_v alone, fp32 streams, aligned rows, whole 32-pixel tiles: grad_v_f32_kernel (planes split once), 512 rows per
+// launch.  K > 64 (AT = 4): the AT = 2 shape with the atoms split over workgroup pairs — D read once, ONE slab per range,
+// so a 512-row batch needs neither a second launch nor a reduce launch.
+template <int AT>
+static int launch_grad_v_f32(const Grad<float>& a) {
+    constexpr int VAT = AT == 4 ? 2 : AT, TW = 32;
+    const int nt = a.P / TW, k_split = AT == 4 ? (a.K + 1) / 2 : 0;
+    const Spread r(nt, AT == 4 ? half_cu() : num_cu());
+    return for_row_chunks(a, 512, r.nwg, [&](int r0, int rows, int rows_p, bool) {
+        auto run = [&](auto kernel, int nw) {
+            const size_t lds = (2 * 3 * (size_t)VAT * 32 * (TW + DPAD) + 3 * (size_t)nw * 32 * (TW + DPAD)) * sizeof(bf16_t);
+            return launch(kernel, dim3(k_split > 0 ? k_split_grid(r.nwg) : r.nwg), dim3(nw * 64), lds, a.st,
+                          a.g + (size_t)r0 * a.P, a.d, a.slab, rows, rows_p, a.P, a.K, nt, r.tpw, k_split,
+                          k_split > 0 ? r.nwg : 0);
+        };
+        if (rows_p > 256) return run(grad_v_f32_kernel<VAT, 16>, 16);
+        if (rows_p > 128) return run(grad_v_f32_kernel<VAT, 8>, 8);
+        return run(grad_v_f32_kernel<VAT, 4>, 4);
+    });
+}
+
+// ---- grad_v alone: grad_v_mfma_kernel, a wave per 32 rows of the chunk ------------------------------------------- //
+template <typename T, int AT, int NW>
+static int launch_grad_v_chunk(const Grad<T>& a, int r0, int rows, int rows_p, const TileSplit& t, const Spread& f,
+                               const Spread& s) {
+    auto run = [&](auto kernel, float* slab, int t0, int t1, const Spread& r) {
+        if (r.nwg <= 0) return 0;
+        return launch(kernel, dim3(r.nwg), dim3(NW * 64), grad_v_lds_bytes<T, AT>(NW), a.st, a.g + (size_t)r0 * a.P, a.d, slab,
+                      rows, rows_p, a.P, a.K, t0, t1, r.tpw);
+    };
+    int rc = run(grad_v_mfma_kernel<T, AT, NW, true>, a.slab, 0, t.nfast, f);
+    if (rc) return rc;
+    return run(grad_v_mfma_kernel<T, AT, NW, false>, a.slab + (size_t)f.nwg * rows_p * a.K, t.nfast, t.ntiles, s);
 }
 
 template <typename T, int AT>
-static int launch_grad_d_lds(const T* g, const float* vp, float* grad_d, int B, int P, int K, int accumulate_d, void* ws,
-                             const GradOpts& o, hipStream_t st) {
-    using E = typename Mma<T>::Elem;
-    constexpr int KA = AT * 32;
-    const int Kp = round_up(K, 16), Bp = round_up(B, 32);
-    const E* vpt;
-    {
-        int rc = transposed_codes<E>(vp, o, ws, Bp, Kp, KA, st, &vpt);
-        if (rc) return rc;
-    }
-    const int ntiles = (P + GV_TW - 1) / GV_TW;
-    const bool vec = (P % 8 == 0) && ((uintptr_t)g % 16 == 0);
-    const int nfast = vec ? P / GV_TW : 0, nslow = ntiles - nfast;
-    const int tpw_fast = nfast > 0 ? (nfast + num_cu() - 1) / num_cu() : 1, nwg_fast = nfast > 0 ? (nfast + tpw_fast - 1) / tpw_fast : 0;
-    const int tpw_slow = nslow > 0 ? (nslow + num_cu() - 1) / num_cu() : 1, nwg_slow = nslow > 0 ? (nslow + tpw_slow - 1) / tpw_slow : 0;
-    for (int r0 = 0; r0 < Bp; r0 += 512) {
-        const int rows_p = imin(Bp - r0, 512), rows = imin(B - r0, rows_p);
-        const T* gc = g + (size_t)r0 * P;
-        const int acc_d = accumulate_d || (r0 > 0);
-        int rc;
-        if (rows_p > 256) {
-            rc = launch_grad_d_lds_nw<T, AT, 8, 2, true>(gc, vpt + r0, Bp, grad_d, rows, rows_p, P, K, acc_d, 0, nfast, nwg_fast, tpw_fast, st);
-            if (rc) return rc;
-            rc = launch_grad_d_lds_nw<T, AT, 8, 2, false>(gc, vpt + r0, Bp, grad_d, rows, rows_p, P, K, acc_d, nfast, ntiles, nwg_slow, tpw_slow, st);
-        } else {
-            rc = launch_grad_d_lds_nw<T, AT, 8, 1, true>(gc, vpt + r0, Bp, grad_d, rows, rows_p, P, K, acc_d, 0, nfast, nwg_fast, tpw_fast, st);
-            if (rc) return rc;
-            rc = launch_grad_d_lds_nw<T, AT, 8, 1, false>(gc, vpt + r0, Bp, grad_d, rows, rows_p, P, K, acc_d, nfast, ntiles, nwg_slow, tpw_slow, st);
+static int launch_grad_v(const Grad<T>& a) {
+    constexpr int kMax = GradVWaves<T, AT>::kMax;
+    const TileSplit t(a.P, GV_TW, a.vec(8));
+    const Spread f(t.nfast, num_cu()), s(t.nslow(), num_cu());
+    return for_row_chunks(a, kMax * 32, f.nwg + s.nwg, [&](int r0, int rows, int rows_p, bool) {
+        const int nwaves = rows_p / 32;
+        if constexpr (kMax >= 16) {
+            if (nwaves > 8) return launch_grad_v_chunk<T, AT, 16>(a, r0, rows, rows_p, t, f, s);
         }
-        if (rc) return rc;
-    }
-    return 0;
+        if constexpr (kMax >= 8) {
+            if (nwaves > 4) return launch_grad_v_chunk<T, AT, 8>(a, r0, rows, rows_p, t, f, s);
+        }
+        return launch_grad_v_chunk<T, AT, 4>(a, r0, rows, rows_p, t, f, s);
+    });
 }
 
-// ---- grad_d alone, fp32 streams, K > 64: the grad_d half of grad_fused_f32_kernel (pre-split operands), 256 rows per launch -- //
-template <int AT>
-static int launch_grad_d_f32_lds(const float* g, const float* vp, float* grad_d, int B, int P, int K, int accumulate_d, void* ws,
-                                 const GradOpts& o, hipStream_t st) {
-    constexpr int KA = AT * 32, NW = 8, TW = 32;
-    const int Kp = round_up(K, 16), Bp = round_up(B, 32);
-    const float* vpt;
-    int rc = transposed_codes<float>(vp, o, ws, Bp, Kp, KA, st, &vpt);
-    if (rc) return rc;
-    const int nt = P / TW, tpw = (nt + num_cu() - 1) / num_cu(), nwg = (nt + tpw - 1) / tpw;
-    const size_t lds = 3 * (size_t)NW * 32 * (TW + DPAD) * sizeof(bf16_t) + (size_t)NW * 16 * 64 * sizeof(float);
-    rc = set_lds((const void*)grad_fused_f32_kernel<AT, NW, false, false>, lds);
-    if (rc) return rc;
-    rc = set_lds((const void*)grad_fused_f32_kernel<AT, NW, true, false>, lds);
-    if (rc) return rc;
-    for (int r0 = 0; r0 < Bp; r0 += NW * 32) {
-        const int rows_p = imin(Bp - r0, NW * 32), rows = imin(B - r0, rows_p);
-        const float* gc = g + (size_t)r0 * P;
-        if (accumulate_d || r0 > 0)
-            hipLaunchKernelGGL((grad_fused_f32_kernel<AT, NW, true, false>), dim3(nwg), dim3(NW * 64), lds, st, gc,
-                               (const float*)nullptr, (const float*)vpt + r0, Bp, grad_d, (float*)nullptr, rows, rows_p, P, K, nt, tpw);
-        else
-            hipLaunchKernelGGL((grad_fused_f32_kernel<AT, NW, false, false>), dim3(nwg), dim3(NW * 64), lds, st, gc,
-                               (const float*)nullptr, (const float*)vpt + r0, Bp, grad_d, (float*)nullptr, rows, rows_p, P, K, nt, tpw);
-        ADIL_CHECK_LAUNCH();
-    }
-    return 0;
-}
-
-template <typename T, int PXT, int AT>
-static int launch_grad_cfg(const T* g, const float* d, const float* vp, float* grad_d, float* grad_vb, int B, int P,
-                           int K, int accumulate_d, void* ws, const GradOpts& o, hipStream_t st) {
-    constexpr int KA = AT * 32;
-    const int Bp = round_up(B, 32);
-    float* slab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(ws) + (((size_t)KA * Bp * sizeof(float) + 255) / 256) * 256);
-    int rc = 0;
-    if constexpr (FusedCfg<T, AT>::kMaxRows > 0) {                 // learning step: both outputs from ONE pass over g
-        // ... while the batch fits four fused launches.  Every row chunk after the first has to ACCUMULATE into grad_d (the
-        // ACC variant: old tile values requested before the next tile's loads so that waiting for them does not drain the
-        // prefetch).  Measured, fused chunks vs the two single-output kernels: bf16 1024 rows K=50 (2 chunks) 128 vs 198 us;
-        // fp32 512 rows K=50 (2 chunks) 233 vs 242 us; bf16 2048 rows K=50 (4 chunks) 248 vs 360 us; bf16 1024 rows K=100
-        // (4 chunks) 291.5 vs 291.3 us; 768 rows K=100 (3 chunks) 214 vs 234 us — with the direct-load grad_d kernel.  With
-        // grad_d through LDS (launch_grad_d_lds) the two single-output kernels win for K > 64 from the second chunk on:
-        // 512 rows 102 vs 135 us, 768 rows 194 vs 214, 1024 rows 253 vs 292.
-        constexpr int kRows = FusedCfg<T, AT>::kMaxRows;
-        // K > 64: a fused launch holds 256 rows only (its grad_v accumulators), so beyond one chunk the two single-output
-        // kernels win once grad_d goes through LDS in 512-row launches (launch_grad_d_lds)
-        if constexpr (AT == 4 && sizeof(T) == 2) {
-            // 64 < K <= 128 on bf16 streams (round 4): the atoms split over workgroup pairs, g read once from HBM, D / grad_d /
-            // slabs moved once (launch_grad_fused_split) — up to four 512-row chunks, like the K <= 64 rule below.
-            // ADIL_GRAD_ATOM_SPLIT=0 keeps the round-3 route (grad_d through LDS + the grad_v kernel) for A/B measurements.
-            static const bool split_on = []() { const char* e = getenv("ADIL_GRAD_ATOM_SPLIT"); return !(e && e[0] == '0'); }();
-            if (grad_d != nullptr && grad_vb != nullptr && split_on && Bp <= 4 * 512)
-                return launch_grad_fused_split<T>(g, d, vp, grad_d, grad_vb, B, P, K, accumulate_d, ws, slab, o, st);
-        }
-        const bool fused = (AT == 4 && sizeof(T) == 2) ? Bp <= kRows : Bp <= 4 * kRows;
-        if (grad_d != nullptr && grad_vb != nullptr && fused)
-            return launch_grad_fused<T, AT>(g, d, vp, grad_d, grad_vb, B, P, K, accumulate_d, ws, slab, o, st);
-    }
+// adil_grad's dispatch, in the order of the route table (ROUTES in tests/test_gpu_routes.py).
+//
+// A learning step wants both outputs from ONE pass over g while the batch fits four fused launches; every row chunk after
+// the first ACCUMULATES into grad_d (the ACC variant: old tile values requested before the next tile's loads so that
+// waiting for them does not drain the prefetch).  Measured, fused chunks vs the two single-output kernels: bf16 1024 rows
+// K=50 (2 chunks) 128 vs 198 us; fp32 512 rows K=50 (2 chunks) 233 vs 242 us; bf16 2048 rows K=50 (4 chunks) 248 vs
+// 360 us.  For K > 64 a fused launch holds 256 rows only (its grad_v accumulators), and the two single-output kernels,
+// grad_d through LDS in 512-row launches, beat it from the second chunk on (512 rows 102 vs 135 us, 768 rows 194 vs 214,
+// 1024 rows 253 vs 292); the atom-split pass beats both.
+template <typename T, int AT>
+static int launch_grad(const Grad<T>& a) {
+    const bool both = a.grad_d != nullptr && a.grad_vb != nullptr;
     if constexpr (AT == 4 && sizeof(T) == 2) {
-        if (grad_d != nullptr) rc = launch_grad_d_lds<T, AT>(g, vp, grad_d, B, P, K, accumulate_d, ws, o, st);
-    } else if constexpr (AT == 4 && sizeof(T) == 4) {
-        if (grad_d != nullptr) {
-            if (P % 32 == 0 && (uintptr_t)g % 16 == 0)
-                rc = launch_grad_d_f32_lds<AT>((const float*)g, vp, grad_d, B, P, K, accumulate_d, ws, o, st);
-            else
-                rc = launch_grad_d<T, PXT, AT>(g, vp, grad_d, B, P, K, accumulate_d, ws, o, st);
-        }
-    } else {
-        if (grad_d != nullptr) rc = launch_grad_d<T, PXT, AT>(g, vp, grad_d, B, P, K, accumulate_d, ws, o, st);
+        // both outputs, bf16, K > 64, Bp <= 2048: the atom-split pass
+        if (both && a.Bp <= 4 * 512) return launch_grad_fused_split(a);
     }
-    if (rc) return rc;
-    if (grad_vb != nullptr) rc = launch_grad_v<T, AT>(g, d, grad_vb, B, P, K, slab, o, st);
-    return rc;
-}
-
-template <typename T>
-static int launch_grad(const void* g, const float* d, const float* vp, float* grad_d, float* grad_vb, int B, int P,
-                       int K, int accumulate_d, void* ws, const GradOpts& o, hipStream_t st) {
-    const int at = grad_at(K);
-    if (at == 1) return launch_grad_cfg<T, 4, 1>((const T*)g, d, vp, grad_d, grad_vb, B, P, K, accumulate_d, ws, o, st);
-    if (at == 2) return launch_grad_cfg<T, 2, 2>((const T*)g, d, vp, grad_d, grad_vb, B, P, K, accumulate_d, ws, o, st);
-    return launch_grad_cfg<T, 2, 4>((const T*)g, d, vp, grad_d, grad_vb, B, P, K, accumulate_d, ws, o, st);
+    if constexpr (AT <= 2) {
+        if (both && a.Bp <= 4 * FusedCfg<T>::kMaxRows) {
+            if constexpr (sizeof(T) == 4) {
+                // both outputs, K <= 64, fp32, P % 32 == 0, g aligned: grad_fused_f32_kernel in 256-row chunks
+                if (a.vec(32)) return launch_grad_fused_f32<AT, true>(a);
+            }
+            // both outputs, K <= 64: generic grad_fused_mfma_kernel, fast and slow ranges
+            return launch_grad_fused<T, AT>(a);
+        }
+    }
+    // otherwise grad_d and grad_v separately
+    if (a.grad_d != nullptr) {
+        int rc;
+        if constexpr (AT == 4 && sizeof(T) == 2) {
+            rc = launch_grad_d_lds(a);                                // grad_d, bf16, K > 64: through LDS, 512-row chunks
+        } else if constexpr (AT == 4) {
+            if (a.vec(32)) rc = launch_grad_fused_f32<4, false>(a);   // grad_d, fp32, K > 64, P % 32 == 0: 256-row chunks
+            else rc = launch_grad_d<T, AT>(a);                        // grad_d, everything else: grad_d_mfma_kernel
+        } else {
+            rc = launch_grad_d<T, AT>(a);                             // grad_d, everything else: grad_d_mfma_kernel
+        }
+        if (rc) return rc;
+    }
+    if (a.grad_vb == nullptr) return 0;
+    if constexpr (sizeof(T) == 4) {
+        if (a.vec(32)) return launch_grad_v_f32<AT>(a);              // grad_v, fp32, P % 32 == 0: grad_v_f32_kernel
+    }
+    return launch_grad_v<T, AT>(a);                                  // grad_v, everything else: grad_v_mfma_kernel chunks
 }
 
 extern "C" int adil_grad_code_rows(int K) { return (K > 0 && K <= ADIL_MAX_ATOMS) ? grad_at(K) * 32 : 0; }
@@ -2815,12 +2576,28 @@ extern "C" int adil_grad(const void* g, const float* d, const float* vp, const v
     if (grad_vb != nullptr && !d) return ADIL_EINVAL;
     if (vpt != nullptr && ((uintptr_t)vpt & 15)) return ADIL_EINVAL;
     if (!ws || ws_bytes < adil_grad_workspace_bytes(B, P, K)) return ADIL_EWORKSPACE;
-    const GradOpts o{vpt, grad_vb != nullptr ? nslabs_out : nullptr};
-    if (dtype == ADIL_F32) return launch_grad<float>(g, d, vp, grad_d, grad_vb, B, P, K, accumulate_d, ws, o, (hipStream_t)stream);
-    if (dtype == ADIL_BF16) return launch_grad<bf16_t>(g, d, vp, grad_d, grad_vb, B, P, K, accumulate_d, ws, o, (hipStream_t)stream);
-    return ADIL_EINVAL;
+    return with_dtype(dtype, [&](auto t) {
+        return with_atom_tiles(K, [&](auto at) {
+            using T = typename decltype(t)::type;
+            using E = typename Mma<T>::Elem;
+            constexpr int AT = decltype(at)::value;
+            const int Bp = round_up(B, 32);
+            float* slab = reinterpret_cast<float*>(reinterpret_cast<unsigned char*>(ws) + adil_grad_slab_offset(B, P, K));
+            Grad<T> a{(const T*)g, d, grad_d, grad_vb, B, Bp, P, K, accumulate_d, reinterpret_cast<const E*>(vpt), slab,
+                      grad_vb != nullptr ? nslabs_out : nullptr, (hipStream_t)stream};
+            if (grad_d != nullptr && vpt == nullptr) {                // the codes transposed here (one small launch)
+                E* vt = reinterpret_cast<E*>(ws);
+                int rc = launch(transpose_codes_kernel<E>, dim3((AT * 32 * Bp + 255) / 256), dim3(256), 0, a.st, vp, Bp,
+                                round_up(K, 16), AT * 32, vt);
+                if (rc) return rc;
+                a.vpt = vt;
+            }
+            return launch_grad<T, AT>(a);
+        });
+    });
 }
 
+// ---- K8: z-step ---------------------------------------------------------------------------------------------------- //
 template <bool FAST>
 static int launch_zstep_range(float* z, float* m, float* sq, const float* d, const float* vp, int B, int P, int K,
                               AdamWHyper hy, float lo, float hi, float* max_abs_delta, int tile0, int ntiles,
@@ -2829,22 +2606,15 @@ static int launch_zstep_range(float* z, float* m, float* sq, const float* d, con
     if (ntiles <= 0) return 0;
     const int Kp = round_up(K, 16);
     const size_t lds = (size_t)DImg<float>::PLANES * SYNTH_TILE * (Kp + DPAD) * sizeof(bf16_t);
+    auto run = [&](auto kernel, int nthreads) {
+        return launch(kernel, dim3(ntiles), dim3(nthreads), lds, st, z, m, sq, d, vp, B, P, K, Kp, hy, lo, hi, max_abs_delta,
+                      tile0, skip_if_below, skip_threshold, clear, dyn);
+    };
     if constexpr (FAST) {
-        if (Kp > 64) {                     // 92 KB of D_dagger planes = one workgroup per CU: 8 waves instead of 4 (as synth)
-            int rc = set_lds((const void*)zstep_mfma_kernel<true, 8>, lds);
-            if (rc) return rc;
-            hipLaunchKernelGGL((zstep_mfma_kernel<true, 8>), dim3(ntiles), dim3(512), lds, st, z, m, sq, d, vp, B, P, K, Kp, hy, lo,
-                               hi, max_abs_delta, tile0, skip_if_below, skip_threshold, clear, dyn);
-            ADIL_CHECK_LAUNCH();
-            return 0;
-        }
+        // 92 KB of D_dagger planes = one workgroup per CU: 8 waves instead of 4 (as synth)
+        if (Kp > 64) return run(zstep_mfma_kernel<true, 8>, 512);
     }
-    int rc = set_lds((const void*)zstep_mfma_kernel<FAST>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((zstep_mfma_kernel<FAST>), dim3(ntiles), dim3(256), lds, st, z, m, sq, d, vp, B, P, K, Kp, hy, lo, hi,
-                       max_abs_delta, tile0, skip_if_below, skip_threshold, clear, dyn);
-    ADIL_CHECK_LAUNCH();
-    return 0;
+    return run(zstep_mfma_kernel<FAST, 4>, 256);
 }
 
 // ---- K8 + K6: z-step that also leaves the next iteration's codes as slabs (zstep_codes_kernel) ---------------------- //
@@ -2875,24 +2645,6 @@ extern "C" size_t adil_zstep_codes_slab_bytes(int B, int P, int K) {
     return (size_t)nwg * round_up(B, 32) * K * sizeof(float);
 }
 
-template <int AT, int RB>
-static int launch_zstep_codes(float* z, float* m, float* sq, const float* d, const float* vp, float* slab, int B, int P, int K,
-                              AdamWHyper hy, float lo, float hi, float* max_abs_delta, const float* skip_if_below,
-                              float skip_threshold, float* clear, const float* dyn, int* nslabs_out, hipStream_t st) {
-    const int Kp = round_up(K, 16), Bp = round_up(B, 32);
-    int nslices, spw, nwg, ny;
-    zstep_codes_grid(B, P, K, &nslices, &spw, &nwg, &ny);
-    if (RB != zstep_codes_row_blocks(B, K)) return ADIL_EINVAL;          // the grid above was cut for another instantiation
-    const size_t lds = (size_t)3 * SYNTH_TILE * ZCodes<AT>::KS * sizeof(bf16_t) + (size_t)8 * 16 * ZC_IS * sizeof(float);
-    int rc = set_lds((const void*)zstep_codes_kernel<AT, RB>, lds);
-    if (rc) return rc;
-    hipLaunchKernelGGL((zstep_codes_kernel<AT, RB>), dim3(nwg, ny), dim3(512), lds, st, z, m, sq, d, vp, slab, B, Bp, P, K, Kp, hy,
-                       lo, hi, max_abs_delta, nslices, spw, skip_if_below, skip_threshold, clear, dyn);
-    ADIL_CHECK_LAUNCH();
-    *nslabs_out = nwg;
-    return 0;
-}
-
 extern "C" int adil_zstep_codes(float* z, float* m, float* s, const float* dpinv_t, const float* gvp, int B, int P, int K,
                                 float decay, float b1, float b2, float eps, float step_size, float bc2_sqrt, float lo, float hi,
                                 float* max_abs_delta, const float* skip_if_below, float skip_threshold, float* clear,
@@ -2905,20 +2657,28 @@ extern "C" int adil_zstep_codes(float* z, float* m, float* s, const float* dpinv
     if (!zstep_codes_shape_ok(B, P, K)) return ADIL_EINVAL;
     if ((((uintptr_t)z | (uintptr_t)m | (uintptr_t)s | (uintptr_t)dpinv_t | (uintptr_t)code_slabs) % 16) != 0) return ADIL_EINVAL;
     if (code_slab_bytes < adil_zstep_codes_slab_bytes(B, P, K)) return ADIL_EWORKSPACE;
-    AdamWHyper hy{decay, b1, b2, eps, step_size, bc2_sqrt};
-    hipStream_t st = (hipStream_t)stream;
-    const int at = atom_tiles(K), Bp = round_up(B, 32);
+    const AdamWHyper hy{decay, b1, b2, eps, step_size, bc2_sqrt};
+    const int Kp = round_up(K, 16), Bp = round_up(B, 32);
+    int nslices, spw, nwg, ny;
+    zstep_codes_grid(B, P, K, &nslices, &spw, &nwg, &ny);
     // accumulators per wave: RB blocks x AT atom tiles <= 4 (64 registers).  One block per wave when the batch leaves the
     // second one empty anyway.
-    if (at == 1) {
-        if (Bp > 256) return launch_zstep_codes<1, 2>(z, m, s, dpinv_t, gvp, code_slabs, B, P, K, hy, lo, hi, max_abs_delta, skip_if_below, skip_threshold, clear, dyn_scalars, nslabs_out, st);
-        return launch_zstep_codes<1, 1>(z, m, s, dpinv_t, gvp, code_slabs, B, P, K, hy, lo, hi, max_abs_delta, skip_if_below, skip_threshold, clear, dyn_scalars, nslabs_out, st);
-    }
-    if (at == 2) {
-        if (Bp > 256) return launch_zstep_codes<2, 2>(z, m, s, dpinv_t, gvp, code_slabs, B, P, K, hy, lo, hi, max_abs_delta, skip_if_below, skip_threshold, clear, dyn_scalars, nslabs_out, st);
-        return launch_zstep_codes<2, 1>(z, m, s, dpinv_t, gvp, code_slabs, B, P, K, hy, lo, hi, max_abs_delta, skip_if_below, skip_threshold, clear, dyn_scalars, nslabs_out, st);
-    }
-    return launch_zstep_codes<4, 1>(z, m, s, dpinv_t, gvp, code_slabs, B, P, K, hy, lo, hi, max_abs_delta, skip_if_below, skip_threshold, clear, dyn_scalars, nslabs_out, st);
+    const bool two_blocks = zstep_codes_row_blocks(B, K) == 2;
+    const int rc = with_atom_tiles(K, [&](auto at) {
+        constexpr int AT = decltype(at)::value;
+        const size_t lds = (size_t)3 * SYNTH_TILE * ZCodes<AT>::KS * sizeof(bf16_t) + (size_t)8 * 16 * ZC_IS * sizeof(float);
+        auto run = [&](auto kernel) {
+            return launch(kernel, dim3(nwg, ny), dim3(512), lds, (hipStream_t)stream, z, m, s, dpinv_t, gvp, code_slabs, B, Bp,
+                          P, K, Kp, hy, lo, hi, max_abs_delta, nslices, spw, skip_if_below, skip_threshold, clear, dyn_scalars);
+        };
+        if constexpr (AT <= 2) {
+            if (two_blocks) return run(zstep_codes_kernel<AT, 2>);
+        }
+        return run(zstep_codes_kernel<AT, 1>);
+    });
+    if (rc) return rc;
+    *nslabs_out = nwg;
+    return 0;
 }
 
 extern "C" int adil_zstep(float* z, float* m, float* s, const float* dpinv_t, const float* gvp, int B, int P, int K,
@@ -2927,16 +2687,15 @@ extern "C" int adil_zstep(float* z, float* m, float* s, const float* dpinv_t, co
                           const float* dyn_scalars, void* stream) {
     ADIL_ENTER();
     if (!z || !m || !s || !dpinv_t || !gvp || B <= 0 || P <= 0 || K <= 0 || K > ADIL_MAX_ATOMS) return ADIL_EINVAL;
-    AdamWHyper hy{decay, b1, b2, eps, step_size, bc2_sqrt};
+    const AdamWHyper hy{decay, b1, b2, eps, step_size, bc2_sqrt};
     const bool vec = (P % 4 == 0) && ((((uintptr_t)z | (uintptr_t)m | (uintptr_t)s | (uintptr_t)dpinv_t) % 16) == 0) &&
                      (P <= (1 << 23));                           // 32-row blocks addressable with 32-bit byte offsets
-    const int ntiles = (P + SYNTH_TILE - 1) / SYNTH_TILE;
-    const int nfast = vec ? P / SYNTH_TILE : 0;
+    const TileSplit t(P, SYNTH_TILE, vec);
     // `clear` is written by the first launch only (tile0 == 0 exists in exactly one of the two ranges)
-    int rc = launch_zstep_range<true>(z, m, s, dpinv_t, gvp, B, P, K, hy, lo, hi, max_abs_delta, 0, nfast, skip_if_below,
-                                      skip_threshold, nfast > 0 ? clear : nullptr, dyn_scalars, (hipStream_t)stream);
+    int rc = launch_zstep_range<true>(z, m, s, dpinv_t, gvp, B, P, K, hy, lo, hi, max_abs_delta, 0, t.nfast, skip_if_below,
+                                      skip_threshold, t.nfast > 0 ? clear : nullptr, dyn_scalars, (hipStream_t)stream);
     if (rc) return rc;
-    return launch_zstep_range<false>(z, m, s, dpinv_t, gvp, B, P, K, hy, lo, hi, max_abs_delta, nfast, ntiles - nfast,
-                                     skip_if_below, skip_threshold, nfast > 0 ? nullptr : clear, dyn_scalars,
+    return launch_zstep_range<false>(z, m, s, dpinv_t, gvp, B, P, K, hy, lo, hi, max_abs_delta, t.nfast, t.nslow(),
+                                     skip_if_below, skip_threshold, t.nfast > 0 ? nullptr : clear, dyn_scalars,
                                      (hipStream_t)stream);
 }

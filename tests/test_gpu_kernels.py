@@ -813,8 +813,9 @@ def test_grad_bf16_many_atoms(b, k, c, h, w):
                                        (257, 100, 3, 9, 7)])
 def test_grad_fp32_many_atoms(b, k, c, h, w):
     """K > 64 on fp32 streams: grad_d alone through the pre-split kernel (grad_fused_f32_kernel without its grad_v half,
-    256 rows per launch, the second chunk accumulates) and grad_v through grad_v_f32_kernel<4> — or the generic kernels
-    when the rows are not whole 32-pixel tiles (9x7).  fp32-grade tolerances against fp64 matmuls, reproducible."""
+    256 rows per launch, the second chunk accumulates) and grad_v through grad_v_f32_kernel<2> with the atoms split over
+    workgroup pairs — or the generic kernels when the rows are not whole 32-pixel tiles (9x7).  fp32-grade tolerances
+    against fp64 matmuls, reproducible."""
     gen = torch.Generator().manual_seed(b + k + h + 5)
     d = (-1 + 2 * torch.rand(c, h, w, k, generator=gen)).to(DEV)
     v = (torch.randn(b, k, generator=gen) * 0.02).to(DEV)

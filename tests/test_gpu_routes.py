@@ -46,7 +46,7 @@ def _zstep_codes_branch(b, k):
     at = (k + 31) // 32                                   # atom_tiles(K); 3 tiles run the 4-tile instantiation
     rb = 2 if at <= 2 and _round_up(b, 32) > 256 else 1
     ny = -(-_round_up(b, 32) // (8 * rb * 32))
-    return f"launch_zstep_codes<AT={at if at <= 2 else 4}, RB={rb}>, {ny} row range(s) of workgroups"
+    return f"adil_zstep_codes: zstep_codes_kernel<AT={at if at <= 2 else 4}, RB={rb}>, {ny} row range(s) of workgroups"
 
 
 # --------------------------------------------------------------------------------------------------- the route table
@@ -57,54 +57,54 @@ ROUTES = [
           (544, 3, 20, 12, 65), BF16, chunks=2),
     Route("grad", "launch_grad_fused_split, slow tail: P%8==0, P%64!=0; three 512-row chunks", (1100, 3, 12, 12, 127), BF16, chunks=3),
     # bf16, K > 64, Bp > 4*512: split off -> grad_d through LDS + generic grad_v, 512-row chunks, a reduce per chunk
-    Route("grad", "launch_grad_cfg Bp>2048: launch_grad_d_lds + launch_grad_v<bf16,4> generic, fast + slow tail",
+    Route("grad", "launch_grad Bp>2048: launch_grad_d_lds + launch_grad_v<bf16,4> generic, fast + slow tail",
           (2080, 3, 12, 12, 100), BF16, chunks=5),
-    Route("grad", "launch_grad_cfg Bp>2048: launch_grad_d_lds + launch_grad_v<bf16,4> generic, P%64==0, 1-row last chunk",
+    Route("grad", "launch_grad Bp>2048: launch_grad_d_lds + launch_grad_v<bf16,4> generic, P%64==0, 1-row last chunk",
           (2049, 3, 8, 8, 128), BF16, chunks=5),
     # bf16 grad_v alone at K > 64 (dL/dv = g D of DDrague at 100 atoms)
     Route("grad_v", "launch_grad_v<bf16,4> generic: one 512-row chunk, 16 waves, all FAST", (512, 3, 224, 224, 100), BF16),
     Route("grad_v", "launch_grad_v<bf16,4> generic: chunks of 512 + 96 rows (16 / 4 waves)", (600, 3, 16, 16, 113), BF16, chunks=2),
     # fp32, K > 64, P%32==0: grad_d through grad_fused_f32_kernel (256-row launches), grad_v on the atom-split kernel
-    Route("grad", "launch_grad_v fp32 AT=4: grad_v_f32_kernel k-split, chunks 512 + 96 (r0 offset, reduce per chunk); "
-          "launch_grad_d_f32_lds", (600, 3, 16, 16, 100), F32, chunks=2),
-    Route("grad", "launch_grad_v fp32 AT=4: grad_v_f32_kernel k-split, chunks 512 + 512 + 32; launch_grad_d_f32_lds",
-          (1030, 3, 8, 8, 128), F32, chunks=3),
+    Route("grad", "launch_grad_v_f32<4>: grad_v_f32_kernel<2> k-split, chunks 512 + 96 (r0 offset, reduce per chunk); "
+          "launch_grad_fused_f32<4> grad_d only", (600, 3, 16, 16, 100), F32, chunks=2),
+    Route("grad", "launch_grad_v_f32<4>: grad_v_f32_kernel<2> k-split, chunks 512 + 512 + 32; "
+          "launch_grad_fused_f32<4> grad_d only", (1030, 3, 8, 8, 128), F32, chunks=3),
     # fp32, K > 64, P%32!=0: the generic kernels with FAST ranges and a slow tail
-    Route("grad", "launch_grad_cfg fp32 AT=4, P%32!=0, P%8==0: launch_grad_d<f32,2,4> + grad_v_mfma<f32,4,4> "
+    Route("grad", "launch_grad fp32 AT=4, P%32!=0, P%8==0: launch_grad_d<f32,4> + grad_v_mfma<f32,4,4> "
           "128-row chunks, fast + slow tail", (300, 3, 12, 12, 100), F32, chunks=3),
     # K <= 64 at two atom tiles beyond the fused limit
-    Route("grad", "launch_grad_cfg bf16 AT=2, Bp>2048 (not fused): launch_grad_d<bf16,2,2> + grad_v_mfma<bf16,2,16>, "
+    Route("grad", "launch_grad bf16 AT=2, Bp>2048 (not fused): launch_grad_d<bf16,2> + grad_v_mfma<bf16,2,16>, "
           "fast + slow tail", (2080, 3, 12, 12, 50), BF16, chunks=5),
-    Route("grad", "launch_grad_cfg fp32 AT=2, Bp>1024 (not fused): launch_grad_d<f32,2,2> + grad_v_f32_kernel<2> "
+    Route("grad", "launch_grad fp32 AT=2, Bp>1024 (not fused): launch_grad_d<f32,2> + launch_grad_v_f32<2> "
           "chunks 512 + 512 + 32", (1030, 3, 16, 16, 50), F32, chunks=3),
     # workgroup shapes picked from the batch: waves per workgroup (NW) and 32-row blocks per wave (RB)
-    Route("grad", "launch_grad_fused_range<bf16,1>: nblk=7 -> NW=8, RB=1; grad_v alone: grad_v_mfma<bf16,1,8>",
+    Route("grad", "launch_grad_fused<bf16,1>: nblk=7 -> NW=8, RB=1; grad_v alone: grad_v_mfma<bf16,1,8>",
           (200, 3, 12, 12, 10), BF16),
-    Route("grad", "launch_grad_fused_range<bf16,1>: nblk=10 -> NW=8, RB=2; grad_v alone: grad_v_mfma<bf16,1,16>",
+    Route("grad", "launch_grad_fused<bf16,1>: nblk=10 -> NW=8, RB=2; grad_v alone: grad_v_mfma<bf16,1,16>",
           (300, 3, 12, 12, 10), BF16),
-    Route("grad", "launch_grad_fused_range<bf16,2>: nblk=7 -> NW=8, RB=1; grad_v alone: grad_v_mfma<bf16,2,8>",
+    Route("grad", "launch_grad_fused<bf16,2>: nblk=7 -> NW=8, RB=1; grad_v alone: grad_v_mfma<bf16,2,8>",
           (200, 3, 12, 12, 50), BF16),
     Route("grad_v", "launch_grad_v<bf16,4> generic: 7 waves -> NW=8", (200, 3, 12, 12, 100), BF16),
     Route("grad", "launch_grad_fused<f32,1> generic (P%32!=0): nblk=7 -> NW=8; grad_v alone: grad_v_mfma<f32,1,8>",
           (200, 3, 12, 12, 10), F32),
     Route("grad", "launch_grad_fused<f32,2> generic (P%32!=0): nblk=7 -> NW=8; grad_v alone: grad_v_mfma<f32,2,8>",
           (200, 3, 12, 12, 50), F32),
-    Route("grad_v", "launch_grad_v fp32 AT=1, P%32==0: grad_v_f32_kernel<1,4> (rows_p <= 128)", (70, 3, 16, 16, 10), F32),
-    Route("grad_v", "launch_grad_v fp32 AT=1, P%32==0: grad_v_f32_kernel<1,8> (128 < rows_p <= 256)", (200, 3, 16, 16, 10), F32),
-    Route("grad_v", "launch_grad_v fp32 AT=1, P%32==0: grad_v_f32_kernel<1,16> (rows_p > 256)", (300, 3, 16, 16, 10), F32),
-    Route("grad_v", "launch_grad_v fp32 AT=2, P%32==0: grad_v_f32_kernel<2,8> (128 < rows_p <= 256)", (200, 3, 16, 16, 50), F32),
+    Route("grad_v", "launch_grad_v_f32<1>, P%32==0: grad_v_f32_kernel<1,4> (rows_p <= 128)", (70, 3, 16, 16, 10), F32),
+    Route("grad_v", "launch_grad_v_f32<1>, P%32==0: grad_v_f32_kernel<1,8> (128 < rows_p <= 256)", (200, 3, 16, 16, 10), F32),
+    Route("grad_v", "launch_grad_v_f32<1>, P%32==0: grad_v_f32_kernel<1,16> (rows_p > 256)", (300, 3, 16, 16, 10), F32),
+    Route("grad_v", "launch_grad_v_f32<2>, P%32==0: grad_v_f32_kernel<2,8> (128 < rows_p <= 256)", (200, 3, 16, 16, 50), F32),
     # g not 16-byte aligned: the `vec` test sends every tile through the element-wise kernels
     Route("grad", "launch_grad_fused<bf16,2>, g unaligned: all tiles slow", (70, 3, 12, 12, 50), BF16, offset=2),
     Route("grad", "launch_grad_fused_split, g unaligned: no fast range, slow slabs from 0", (70, 3, 12, 12, 100), BF16, offset=2),
     Route("grad", "launch_grad_fused<f32,2> generic (not grad_fused_f32_kernel), g unaligned: all tiles slow",
           (70, 3, 16, 16, 50), F32, offset=1),
-    Route("grad", "launch_grad_cfg fp32 AT=4, g unaligned: launch_grad_d<f32,2,4> + grad_v_mfma<f32,4,4>, all slow",
+    Route("grad", "launch_grad fp32 AT=4, g unaligned: launch_grad_d<f32,4> + grad_v_mfma<f32,4,4>, all slow",
           (70, 3, 16, 16, 100), F32, offset=1),
-    # synth: x / out not 16-byte aligned -> launch_synth_x runs no FAST tile
-    Route("synth", "launch_synth_x, x / out unaligned: element-wise tiles only, Kp<=64", (70, 3, 12, 12, 33), F32, offset=1),
-    Route("synth", "launch_synth_x, x / out unaligned: element-wise tiles only, Kp>64", (70, 3, 12, 12, 100), F32, offset=1),
-    Route("synth", "launch_synth_x, x / out unaligned: element-wise tiles only, Kp<=64", (70, 3, 12, 12, 33), BF16, offset=2),
-    Route("synth", "launch_synth_x, x / out unaligned: element-wise tiles only, Kp>64", (70, 3, 12, 12, 100), BF16, offset=2),
+    # synth: x / out not 16-byte aligned -> launch_synth_tiles runs no FAST tile
+    Route("synth", "launch_synth_tiles, x / out unaligned: element-wise tiles only, Kp<=64", (70, 3, 12, 12, 33), F32, offset=1),
+    Route("synth", "launch_synth_tiles, x / out unaligned: element-wise tiles only, Kp>64", (70, 3, 12, 12, 100), F32, offset=1),
+    Route("synth", "launch_synth_tiles, x / out unaligned: element-wise tiles only, Kp<=64", (70, 3, 12, 12, 33), BF16, offset=2),
+    Route("synth", "launch_synth_tiles, x / out unaligned: element-wise tiles only, Kp>64", (70, 3, 12, 12, 100), BF16, offset=2),
     # adil_zstep (unfused) where DDragueSolver must use it: Kp > 112, with and without a 128-pixel tail
     *[Route("zstep", f"adil_zstep: 8-wave FAST kernel (Kp={_round_up(k, 16)} > 64) + {tail}", (40,) + chw + (k,), F32)
       for k in (113, 120, 128) for chw, tail in (((3, 16, 16), "no tail (P%128==0)"), ((3, 12, 12), "element-wise tail (P%128==48)"))],
@@ -123,14 +123,14 @@ def _sweep_grad_branch(dt, k):
     if dt == BF16:
         return f"launch_grad_fused_split: {tail}" if k > 64 else f"launch_grad_fused<bf16,{_grad_at(k)}>: {tail}"
     if k > 64:
-        return f"launch_grad_cfg fp32 AT=4, P%32!=0: launch_grad_d<f32,2,4> + grad_v_mfma<f32,4,4>: {tail}"
+        return f"launch_grad fp32 AT=4, P%32!=0: launch_grad_d<f32,4> + grad_v_mfma<f32,4,4>: {tail}"
     return f"launch_grad_fused<f32,{_grad_at(k)}> generic (P%32!=0): {tail}"
 
 
 def _sweep_synth_branch(dt, k):
     kp = _round_up(k, 16)
     variant = (" (HOIST=8)" if dt == BF16 else " (8 waves)") if kp > 64 else ""
-    return f"launch_synth_x: 3 FAST tiles{variant} + element-wise tail (P%128==48), Kp={kp}"
+    return f"launch_synth_tiles: 3 FAST tiles{variant} + element-wise tail (P%128==48), Kp={kp}"
 
 
 # the K sweep: one ragged batch, P = 3*12*12 = 432 (a multiple of 8, not of 64 or 128): fast ranges and a tail both run
