@@ -3,7 +3,9 @@
 //                               gather) as GEMMs with the BatchNorm / residual / ReLU epilogue (and
 //                               the previous layer's BatchNorm + ReLU as a prologue) applied on chip, forward and input
 //                               gradient
-//   conv3x3                     3x3 / stride-1 convolutions as an implicit GEMM with linear pixel tiling
+//   pw_join                     conv3 of a bottleneck and conv1 of the next one as one kernel, forward and input
+//                               gradient (the C-channel tensor between them stays on chip)
+//   conv3x3                    3x3 / stride-1 convolutions as an implicit GEMM with linear pixel tiling
 // Not part of the ADiL maths: the parity target is plain PyTorch (tests/test_gpu_stem.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -431,6 +433,324 @@ extern "C" int adil_pw_conv_fwd(const void* x, const void* w, const float* scale
     }
     if (N % 128 == 0) return launch_pw_fwd<128, false>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
     return launch_pw_fwd<64, false>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+}
+
+// =========================================================================================================== //
+// Residual join of two consecutive bottlenecks of one stage as ONE kernel: conv3 of block i-1 (width WD -> C = 4 WD,
+// bn2 + ReLU prologue, bn3 + residual + ReLU epilogue) and conv1 of block i (C -> WD, bn1 + ReLU), or the input
+// gradient of the pair.  The C-channel tensor between the two GEMMs (`out` forward, the conv1 input gradient `t`
+// backward) never goes through HBM as an operand:
+//   forward   X0 = relu(h2raw * pscale2 + pshift2)              [128 px][WD], staged once
+//             per 64-channel chunk j of C:  A_j = X0 . W3[j]^T -> bn3 + res + ReLU -> out[:, j] (stored, and kept in
+//             LDS as the K chunk j of GEMM 2)                    B += out[:, j] . W1[:, j]^T
+//             h1 = relu(B * scale1 + shift1)
+//   backward  X0 = (g_h1 * [h1 > 0] * scale1)                   per chunk j:  t_j = bf16(X0 . Wt1[j]^T),
+//             v = t_j + g_out[:, j],  gres[:, j] = v * [out > 0],  G += (v * scale3 * [out > 0]) . Wt3[:, j]^T
+//             gx = G * [h2raw * pscale2 + pshift2 > 0] * pscale2
+// Every value is rounded where pw_conv_fwd / pw_conv_bwd round it and every accumulator sees the same MFMA sequence
+// (chunk j of C is the 64-wide K chunk j of the second GEMM), so the results are bitwise those of the two-kernel route.
+// Workgroup = 128 pixels (4 waves x 32), MFMA roles as in pw_conv_*.  X0 rows, the mid chunk and the output
+// transposes are private to the wave that owns the pixels; only the two weight chunks are shared (2 barriers / chunk).
+// LDS: X0 [128][WD+8] | Wa chunk [64][WD+8] | Wb chunk [WD][72] | mid [128][72]:  54 KB at WD = 64 (2 workgroups per
+// CU), 87 KB at WD = 128 (1).  The epilogue inputs of chunk j+1 (residual / g_out, out) are loaded under chunk j.
+// =========================================================================================================== //
+namespace {
+
+struct JoinArgs {
+    const bf16_t* x0;       // fwd: h2raw [M][WD]         bwd: g_h1 [M][WD]
+    const bf16_t* y0;       //                            bwd: h1 [M][WD] (ReLU mask)
+    const float* s0;        // fwd: pscale2 [WD]          bwd: scale1 [WD]
+    const float* b0;        // fwd: pshift2 [WD]
+    const bf16_t* wa;       // [C][WD]  fwd: conv3 weight, bwd: conv1 weight transposed
+    const float* sa;        // [C]      scale3
+    const float* ba;        // [C]      fwd: shift3
+    const bf16_t* ra;       // [M][C]   fwd: residual     bwd: g_out
+    const bf16_t* ya;       // [M][C]                     bwd: out (ReLU mask)
+    bf16_t* oa;             // [M][C]   fwd: out          bwd: gres
+    const bf16_t* wb;       // [WD][C]  fwd: conv1 weight, bwd: conv3 weight transposed
+    const float* sb;        // [WD]     fwd: scale1       bwd: pscale2
+    const float* bb;        // [WD]     fwd: shift1       bwd: pshift2
+    const bf16_t* xin;      // [M][WD]                    bwd: h2raw
+    bf16_t* ob;             // [M][WD]  fwd: h1           bwd: gx
+    int M, C;
+};
+
+template <int WD, bool BWD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(WD == 64 ? 2 : 1))) void pw_join_kernel(JoinArgs p) {
+    constexpr int XS = WD + 8;                           // X0 / output-transpose row stride (elements): odd x 16 B
+    constexpr int CTB = WD / 32;                         // second GEMM: channel tiles per wave
+    constexpr int X0C = WD / 16;                         // 16-byte chunks of a wave's 32 X0 rows per lane
+    constexpr int WAC = WD / 32;                         // ... of a Wa chunk [64][WD] per thread
+    constexpr int WBC = WD / 32;                         // ... of a Wb chunk [WD][64] per thread
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    bf16_t* sx0 = reinterpret_cast<bf16_t*>(smem_raw);   // [128][XS]
+    bf16_t* swa = sx0 + PW_BM * XS;                      // [64][XS]
+    bf16_t* swb = swa + 64 * XS;                         // [WD][PW_LS]
+    bf16_t* smid = swb + WD * PW_LS;                     // [128][PW_LS]
+    __shared__ __attribute__((aligned(16))) float stab[2 * 4 * 128];   // scale3 | shift3 (C <= 512)
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
+    const int M = p.M, C = p.C, nch = C / 64;
+    const int m0 = blockIdx.x * PW_BM;
+    const int m = m0 + w * 32 + c;                       // this lane's pixel in the epilogues
+    const size_t mc = (size_t)(m < M ? m : M - 1);
+    bf16_t* sxw = sx0 + w * 32 * XS;                     // this wave's X0 rows (later: its output transpose)
+    bf16_t* smw = smid + w * 32 * PW_LS;                 // this wave's mid rows
+
+    u32x4 ar[WAC], br[WBC];
+    auto load_w = [&](int j) {
+#pragma unroll
+        for (int i = 0; i < WAC; ++i) {
+            const int id = tid + 256 * i, row = id / (WD / 8), ch = id % (WD / 8);
+            ar[i] = *reinterpret_cast<const u32x4*>(p.wa + (size_t)(64 * j + row) * WD + ch * 8);
+        }
+#pragma unroll
+        for (int i = 0; i < WBC; ++i) {
+            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
+            br[i] = *reinterpret_cast<const u32x4*>(p.wb + (size_t)row * C + 64 * j + ch * 8);
+        }
+    };
+    auto store_w = [&]() {
+#pragma unroll
+        for (int i = 0; i < WAC; ++i) {
+            const int id = tid + 256 * i, row = id / (WD / 8), ch = id % (WD / 8);
+            *reinterpret_cast<u32x4*>(swa + row * XS + ch * 8) = ar[i];
+        }
+#pragma unroll
+        for (int i = 0; i < WBC; ++i) {
+            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
+            *reinterpret_cast<u32x4*>(swb + row * PW_LS + ch * 8) = br[i];
+        }
+    };
+    // epilogue inputs of a chunk in the accumulator layout: lane = pixel m, quad q of tile ct = channels 32ct+8q+4h..+3
+    u32x2 er[2][4], ey[BWD ? 2 : 1][4];
+    auto load_e = [&](int j) {
+        const bf16_t* rp = p.ra + mc * C + 64 * j + 4 * h;
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) er[ct][q] = *reinterpret_cast<const u32x2*>(rp + 32 * ct + 8 * q);
+        if (BWD) {
+            const bf16_t* yp = p.ya + mc * C + 64 * j + 4 * h;
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                for (int q = 0; q < 4; ++q) ey[BWD ? ct : 0][q] = *reinterpret_cast<const u32x2*>(yp + 32 * ct + 8 * q);
+        }
+    };
+
+    // X0: this wave's 32 pixels, transformed on the way to LDS exactly as pw_conv_fwd's prologue (forward) or
+    // pw_conv_bwd's operand path without g2 (backward) transforms them
+    {
+        u32x4 xr[X0C], yr[BWD ? X0C : 1];
+#pragma unroll
+        for (int i = 0; i < X0C; ++i) {
+            const int id = lane + 64 * i, r = id / (WD / 8), ch = id % (WD / 8);
+            const int mm = m0 + w * 32 + r;
+            const size_t at = (size_t)(mm < M ? mm : M - 1) * WD + ch * 8;
+            xr[i] = *reinterpret_cast<const u32x4*>(p.x0 + at);
+            if (BWD) yr[BWD ? i : 0] = *reinterpret_cast<const u32x4*>(p.y0 + at);
+        }
+        load_w(0);
+        load_e(0);
+        if (tid < C / 4) *reinterpret_cast<float4*>(stab + 4 * tid) = *reinterpret_cast<const float4*>(p.sa + 4 * tid);
+        if (!BWD && tid < C / 4) *reinterpret_cast<float4*>(stab + C + 4 * tid) = *reinterpret_cast<const float4*>(p.ba + 4 * tid);
+#pragma unroll
+        for (int i = 0; i < X0C; ++i) {
+            const int id = lane + 64 * i, r = id / (WD / 8), ch = id % (WD / 8);
+            const f32x2* ps = reinterpret_cast<const f32x2*>(p.s0 + ch * 8);
+            u32x4 t = xr[i];
+            if (BWD) {
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const f32x2 v = bf2_to_f32x2(t[j]);
+                    t[j] = f32x2_to_bf2(v * ps[j]) & pos_mask_bf2(yr[BWD ? i : 0][j]);
+                }
+            } else {
+                const f32x2* pb = reinterpret_cast<const f32x2*>(p.b0 + ch * 8);
+#pragma unroll
+                for (int j = 0; j < 4; ++j) t[j] = relu_bf2(f32x2_to_bf2(bf2_to_f32x2(t[j]) * ps[j] + pb[j]));
+            }
+            *reinterpret_cast<u32x4*>(sxw + r * XS + ch * 8) = t;
+        }
+    }
+    store_w();
+    __syncthreads();
+
+    f32x16 accb[CTB];
+#pragma unroll
+    for (int ct = 0; ct < CTB; ++ct)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accb[ct][r] = 0.0f;
+    const bf16_t* bx = sxw + c * XS + 8 * h;
+    const bf16_t* bm = smw + c * PW_LS + 8 * h;
+    for (int j = 0; j < nch; ++j) {
+        if (j + 1 < nch) load_w(j + 1);
+        // GEMM 1: 32 px x 64 channels of chunk j per wave, K = WD in the k order of the two-kernel route
+        f32x16 acca[2];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acca[ct][r] = 0.0f;
+        const bf16_t* ba = swa + c * XS + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < WD / 16; ++ks) {
+            const bf16x8 b = lds8(bx + 16 * ks);
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct) mma16(acca[ct], lds8(ba + ct * 32 * XS + 16 * ks), b);
+        }
+        // chunk epilogue on the accumulators -> this wave's mid rows
+        u32x2 gz[BWD ? 2 : 1][4];
+#pragma unroll
+        for (int ct = 0; ct < 2; ++ct) {
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int co = 32 * ct + 8 * q + 4 * h;
+                const f32x2* sc = reinterpret_cast<const f32x2*>(stab + 64 * j + co);
+                u32x2 t;
+                if (BWD) {
+                    u32x2 z;
+#pragma unroll
+                    for (int e = 0; e < 2; ++e) {
+                        const f32x2 v = bf2_to_f32x2(pack2_bf16(acca[ct][4 * q + 2 * e], acca[ct][4 * q + 2 * e + 1])) +
+                                        bf2_to_f32x2(er[ct][q][e]);
+                        const unsigned mk = pos_mask_bf2(ey[BWD ? ct : 0][q][e]);
+                        t[e] = f32x2_to_bf2(v) & mk;
+                        z[e] = f32x2_to_bf2(v * sc[e]) & mk;
+                    }
+                    gz[BWD ? ct : 0][q] = z;
+                } else {
+                    const f32x2* sh = reinterpret_cast<const f32x2*>(stab + C + 64 * j + co);
+                    f32x2 v0 = f32x2{acca[ct][4 * q], acca[ct][4 * q + 1]} * sc[0] + sh[0];
+                    f32x2 v1 = f32x2{acca[ct][4 * q + 2], acca[ct][4 * q + 3]} * sc[1] + sh[1];
+                    v0 += bf2_to_f32x2(er[ct][q][0]);
+                    v1 += bf2_to_f32x2(er[ct][q][1]);
+                    t[0] = relu_bf2(f32x2_to_bf2(v0));
+                    t[1] = relu_bf2(f32x2_to_bf2(v1));
+                }
+                *reinterpret_cast<u32x2*>(smw + c * PW_LS + co) = t;
+            }
+        }
+        if (j + 1 < nch) load_e(j + 1);                 // flies under GEMM 2 and the next chunk's GEMM 1
+        // out (forward) / gres (backward) chunk: 16-byte stores from the transposed rows
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int id = lane + 64 * i, px = id >> 3, ch = id & 7;
+            const u32x4 t = *reinterpret_cast<const u32x4*>(smw + px * PW_LS + ch * 8);
+            const int mm = m0 + w * 32 + px;
+            if (mm < M) *reinterpret_cast<u32x4*>(p.oa + (size_t)mm * C + 64 * j + ch * 8) = t;
+        }
+        if (BWD) {                                      // the operand of GEMM 2 is the scaled chunk, not gres
+#pragma unroll
+            for (int ct = 0; ct < 2; ++ct)
+#pragma unroll
+                for (int q = 0; q < 4; ++q)
+                    *reinterpret_cast<u32x2*>(smw + c * PW_LS + 32 * ct + 8 * q + 4 * h) = gz[BWD ? ct : 0][q];
+        }
+        // GEMM 2: chunk j is the 64-wide K chunk j
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const bf16x8 b = lds8(bm + 16 * ks);
+#pragma unroll
+            for (int ct = 0; ct < CTB; ++ct) mma16(accb[ct], lds8(swb + (ct * 32 + c) * PW_LS + 8 * h + 16 * ks), b);
+        }
+        lds_barrier();                                  // every wave is done with this chunk's weights
+        if (j + 1 < nch) {
+            store_w();
+            lds_barrier();
+        }
+    }
+    // final epilogue through this wave's X0 rows (nobody else reads them) -> 16-byte stores of h1 / gx
+#pragma unroll
+    for (int ct = 0; ct < CTB; ++ct) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const int co = 32 * ct + 8 * q + 4 * h;
+            u32x2 t;
+            if (BWD) {
+                t[0] = pack2_bf16(accb[ct][4 * q], accb[ct][4 * q + 1]);
+                t[1] = pack2_bf16(accb[ct][4 * q + 2], accb[ct][4 * q + 3]);
+            } else {
+                const f32x2* sc = reinterpret_cast<const f32x2*>(p.sb + co);
+                const f32x2* sh = reinterpret_cast<const f32x2*>(p.bb + co);
+                f32x2 v0 = f32x2{accb[ct][4 * q], accb[ct][4 * q + 1]} * sc[0] + sh[0];
+                f32x2 v1 = f32x2{accb[ct][4 * q + 2], accb[ct][4 * q + 3]} * sc[1] + sh[1];
+                t[0] = relu_bf2(f32x2_to_bf2(v0));
+                t[1] = relu_bf2(f32x2_to_bf2(v1));
+            }
+            *reinterpret_cast<u32x2*>(sxw + c * XS + co) = t;
+        }
+    }
+    constexpr int CPP = WD / 8;
+#pragma unroll
+    for (int i = 0; i < 32 * CPP / 64; ++i) {
+        const int id = lane + 64 * i, px = id / CPP, ch = id - px * CPP;
+        u32x4 t = *reinterpret_cast<const u32x4*>(sxw + px * XS + ch * 8);
+        const int mm = m0 + w * 32 + px;
+        if (mm < M) {
+            if (BWD) {
+                float v[8], xv[8];
+                unpack8(t, v);
+                unpack8(*reinterpret_cast<const u32x4*>(p.xin + (size_t)mm * WD + ch * 8), xv);
+                const float4 a0 = *reinterpret_cast<const float4*>(p.sb + ch * 8);
+                const float4 a1 = *reinterpret_cast<const float4*>(p.sb + ch * 8 + 4);
+                const float4 b0 = *reinterpret_cast<const float4*>(p.bb + ch * 8);
+                const float4 b1 = *reinterpret_cast<const float4*>(p.bb + ch * 8 + 4);
+                const float ps[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
+                const float pb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+#pragma unroll
+                for (int e = 0; e < 8; ++e) v[e] = (xv[e] * ps[e] + pb[e] > 0.0f) ? v[e] * ps[e] : 0.0f;
+                t = pack8(v);
+            }
+            *reinterpret_cast<u32x4*>(p.ob + (size_t)mm * WD + ch * 8) = t;
+        }
+    }
+}
+
+template <int WD, bool BWD>
+int launch_pw_join(const JoinArgs& a, hipStream_t st) {
+    const size_t lds = ((size_t)(PW_BM + 64) * (WD + 8) + (size_t)(WD + PW_BM) * PW_LS) * sizeof(bf16_t);
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)pw_join_kernel<WD, BWD>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL((pw_join_kernel<WD, BWD>), dim3((unsigned)((a.M + PW_BM - 1) / PW_BM)), dim3(256), lds, st, a);
+    ADIL_CHECK_LAUNCH();
+    return 0;
+}
+
+template <bool BWD>
+int launch_pw_join_w(const JoinArgs& a, int W, hipStream_t st) {
+    if (W == 64) return launch_pw_join<64, BWD>(a, st);
+    return launch_pw_join<128, BWD>(a, st);
+}
+
+}  // namespace
+
+extern "C" int adil_pw_join_fwd(const void* h2raw, const float* pscale2, const float* pshift2, const void* w3,
+                                const float* scale3, const float* shift3, const void* res, void* out, const void* w1,
+                                const float* scale1, const float* shift1, void* h1, int M, int W, int C, void* stream) {
+    ADIL_ENTER();
+    if (!h2raw || !pscale2 || !pshift2 || !w3 || !scale3 || !shift3 || !res || !out || !w1 || !scale1 || !shift1 || !h1 ||
+        M <= 0 || (W != 64 && W != 128) || C != 4 * W)
+        return ADIL_EINVAL;
+    const JoinArgs a = {(const bf16_t*)h2raw, nullptr, pscale2, pshift2, (const bf16_t*)w3, scale3, shift3,
+                        (const bf16_t*)res, nullptr, (bf16_t*)out, (const bf16_t*)w1, scale1, shift1, nullptr, (bf16_t*)h1,
+                        M, C};
+    return launch_pw_join_w<false>(a, W, (hipStream_t)stream);
+}
+
+extern "C" int adil_pw_join_bwd(const void* g_h1, const void* h1, const float* scale1, const void* wt1, const void* g_out,
+                                const void* out, const float* scale3, void* gres, const void* wt3, const void* h2raw,
+                                const float* pscale2, const float* pshift2, void* gx, int M, int W, int C, void* stream) {
+    ADIL_ENTER();
+    if (!g_h1 || !h1 || !scale1 || !wt1 || !g_out || !out || !scale3 || !gres || !wt3 || !h2raw || !pscale2 || !pshift2 ||
+        !gx || M <= 0 || (W != 64 && W != 128) || C != 4 * W)
+        return ADIL_EINVAL;
+    const JoinArgs a = {(const bf16_t*)g_h1, (const bf16_t*)h1, scale1, nullptr, (const bf16_t*)wt1, scale3, nullptr,
+                        (const bf16_t*)g_out, (const bf16_t*)out, (bf16_t*)gres, (const bf16_t*)wt3, pscale2, pshift2,
+                        (const bf16_t*)h2raw, (bf16_t*)gx, M, C};
+    return launch_pw_join_w<true>(a, W, (hipStream_t)stream);
 }
 
 // =========================================================================================================== //

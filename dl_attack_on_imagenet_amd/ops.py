@@ -844,6 +844,68 @@ def pointwise_conv_affine(x: Tensor, w2d: Tensor, wt2d: Tensor, scale: Tensor, s
     return PointwiseConvFunction.apply(x, res, w2d, wt2d, scale, shift, relu, outputs, pscale, pshift, stride2)
 
 
+# widths whose residual joins run as one kernel (adil_pw_join_*), by measurement (ResNet-50, B = 512, MI355X):
+#   width 64  (stage 1): fwd 448 us vs 607 us for the two kernels, bwd 702 us vs 920 us       -> joined
+#   width 128 (stage 2): fwd 348 us vs 325 us, bwd 550 us vs 515 us: 87 KB of LDS leave one workgroup (4 waves) per
+#                        CU, too few to keep HBM busy                                          -> two kernels
+#   width 256 / 512: not in the C ABI (ADIL_EINVAL)                                            -> two kernels
+JOIN_WIDTHS = (64,)
+
+
+class PointwiseJoinFunction(torch.autograd.Function):
+    """The residual join of two bottlenecks of one stage as ONE kernel each way (adil_pw_join_fwd / _bwd):
+    conv3 of block i-1 (bn2 + ReLU prologue on its RAW 3x3 input h2raw, bn3 + residual x + ReLU epilogue) and conv1 of
+    block i (bn1 + ReLU).  (h2raw, x) -> (out, h1); backward (g_out, g_h1) -> (g_h2raw, g_x).  out is needed only as
+    the next join's residual, so g_out is that join's g_x and the skip gradient chains without an autograd add.  The
+    results are bitwise those of the two PointwiseConvFunction calls it replaces."""
+
+    @staticmethod
+    def forward(ctx, h2raw, x, w3, wt3, scale2, shift2, scale3, shift3, w1, wt1, scale1, shift1):
+        lib = _lib.load()
+        b, wd, h, w = h2raw.shape
+        c = w3.shape[0]
+        h2 = h2raw.permute(0, 2, 3, 1)
+        if not h2.is_contiguous():
+            h2 = h2.contiguous()
+        r2 = x.permute(0, 2, 3, 1)
+        if not r2.is_contiguous():
+            r2 = r2.contiguous()
+        out = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=h2raw.device)
+        h1 = torch.empty((b, h, w, wd), dtype=torch.bfloat16, device=h2raw.device)
+        if b > 0:                                                     # empty batches pass through like plain torch modules
+            _lib.check(lib.adil_pw_join_fwd(_ptr(h2), _ptr(scale2), _ptr(shift2), _ptr(w3), _ptr(scale3), _ptr(shift3),
+                                            _ptr(r2), _ptr(out), _ptr(w1), _ptr(scale1), _ptr(shift1), _ptr(h1), b * h * w,
+                                            wd, c, _stream()), "adil_pw_join_fwd")
+        ctx.save_for_backward(h2, out, h1, wt3, scale2, shift2, scale3, wt1, scale1)
+        return out.permute(0, 3, 1, 2), h1.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g_out, g_h1):
+        lib = _lib.load()
+        h2, out, h1, wt3, scale2, shift2, scale3, wt1, scale1 = ctx.saved_tensors
+
+        def nhwc(t):
+            t2 = t.permute(0, 2, 3, 1)
+            return t2 if (t2.is_contiguous() and t2.dtype == torch.bfloat16) else t2.to(torch.bfloat16).contiguous()
+
+        go, gh = nhwc(g_out), nhwc(g_h1)
+        b, h, w, c = out.shape
+        wd = h1.shape[3]
+        gx = torch.empty_like(h2)
+        gres = torch.empty_like(out)
+        if b > 0:
+            _lib.check(lib.adil_pw_join_bwd(_ptr(gh), _ptr(h1), _ptr(scale1), _ptr(wt1), _ptr(go), _ptr(out), _ptr(scale3),
+                                            _ptr(gres), _ptr(wt3), _ptr(h2), _ptr(scale2), _ptr(shift2), _ptr(gx), b * h * w,
+                                            wd, c, _stream()), "adil_pw_join_bwd")
+        return (gx.permute(0, 3, 1, 2), gres.permute(0, 3, 1, 2)) + (None,) * 10
+
+
+def pointwise_join(h2raw: Tensor, x: Tensor, w3: Tensor, wt3: Tensor, pre: Tuple[Tensor, Tensor], scale3: Tensor,
+                   shift3: Tensor, w1: Tensor, wt1: Tensor, scale1: Tensor, shift1: Tensor):
+    """(out, h1) of a residual join (PointwiseJoinFunction); pre = (scale2, shift2) of the 3x3 convolution's bn2."""
+    return PointwiseJoinFunction.apply(h2raw, x, w3, wt3, pre[0], pre[1], scale3, shift3, w1, wt1, scale1, shift1)
+
+
 # --------------------------------------------------------------------------- #
 def pack_conv3x3_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
     """(N,C,3,3) conv weight -> the two bf16 layouts of adil_conv3x3 (include/adil_hip.h), both 2-D:

@@ -10,7 +10,7 @@ are randomly initialised from a seed (synthetic throughput / plumbing runs).
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import torch
 import torch.nn as nn
@@ -706,10 +706,21 @@ class _FusedResBlock(nn.Module):
         self.down = None if block.downsample is None else _ConvAffine(block.downsample[0], block.downsample[1], False)
         self.emit_sub = False            # set by FusedResNet: the NEXT block has a stride-2 pointwise downsample
 
-    def forward(self, x):
+    def joins(self, nxt) -> bool:
+        """This block's conv3 and `nxt`'s conv1 can run as one residual-join kernel (ops.PointwiseJoinFunction): two
+        bottlenecks of one stage (nxt has no downsample) at a width the join kernels cover."""
+        from . import ops
+        return (self.bottleneck and nxt.bottleneck and nxt.down is None and not self.emit_sub
+                and self.c3.pointwise and nxt.c1.pointwise and self.c3.conv.in_channels in ops.JOIN_WIDTHS
+                and nxt.c1.conv.out_channels == self.c3.conv.in_channels
+                and nxt.c1.conv.in_channels == self.c3.conv.out_channels == 4 * self.c3.conv.in_channels)
+
+    def forward(self, x, h1=None, nxt=None):
         """x is a tensor, a (main, skip) pair or a (main, skip, skip[:, :, ::2, ::2]) triple of the same activation (see
         _ConvAffine.forward): the pair keeps the two gradients of the residual join apart until the producing kernel's
-        backward adds them; the third member feeds a stride-2 downsample convolution without a copy."""
+        backward adds them; the third member feeds a stride-2 downsample convolution without a copy.
+        h1: this block's conv1 output, already made by the previous block's join kernel.  nxt: the next block (see
+        joins()); when the join kernel runs, the result is _Joined(out, h1 of nxt)."""
         xm, xs, xsub = (x + (None,))[:3] if isinstance(x, tuple) else (x, x, None)
         if self.down is None:
             idt = xs
@@ -717,17 +728,31 @@ class _FusedResBlock(nn.Module):
             idt = self.down(xsub, strided_view=True)
         else:
             idt = self.down(xs)
-        out = self.c1(xm)
+        out = self.c1(xm) if h1 is None else h1
         if self.bottleneck:
             n_out = 3 if self.emit_sub else 2
             raw = self.c2.raw_conv(out)                                  # 3x3 convolution, no epilogue pass:
             if (self.c2.relu and self.c3.fused_pointwise(raw) and self.c3.conv.in_channels <= 512
                     and raw.is_contiguous(memory_format=torch.channels_last)):
+                if nxt is not None and idt.dtype == torch.bfloat16:
+                    from . import ops
+                    c3, c1 = self.c3, nxt.c1
+                    w3 = c3.conv.weight.reshape(c3.conv.out_channels, c3.conv.in_channels)
+                    w1 = c1.conv.weight.reshape(c1.conv.out_channels, c1.conv.in_channels)
+                    if w3.is_contiguous() and w1.is_contiguous():
+                        return _Joined(*ops.pointwise_join(raw, idt, w3, c3.wt2d, (self.c2.scale, self.c2.shift), c3.scale,
+                                                           c3.shift, w1, c1.wt2d, c1.scale, c1.shift))
                 return self.c3(raw, res=idt, outputs=n_out, pre=(self.c2.scale, self.c2.shift))   # bn2+ReLU run inside c3
             from . import ops
             out = ops.affine_act(raw, self.c2.scale.float(), self.c2.shift.float(), relu=self.c2.relu)
             return self.c3(out, res=idt, outputs=n_out)
         return self.c2(out, res=idt)
+
+
+class _Joined(NamedTuple):
+    """What a block hands on when its conv3 ran as one kernel with the next block's conv1."""
+    out: torch.Tensor
+    h1: torch.Tensor
 
 
 class _FusedStem(_Fp32Tables):
@@ -789,7 +814,7 @@ class FusedResNet(nn.Module):
     cost) — while dictionaries LEARNED against the fp32 head came out consistently a little worse than those learned
     against the bf16 head (profiles/r04_asr_gap.md)."""
 
-    def __init__(self, net: ResNet, normalize=None, head_fp32=False):
+    def __init__(self, net: ResNet, normalize=None, head_fp32=False, chain_joins=True):
         super().__init__()
         if head_fp32 not in (False, True, "inference"):
             raise ValueError("head_fp32 must be False, True or 'inference'")
@@ -807,11 +832,20 @@ class FusedResNet(nn.Module):
         blocks = list(self.layers)
         for cur, nxt in zip(blocks[:-1], blocks[1:]):
             cur.emit_sub = bool(cur.bottleneck and nxt.down is not None and nxt.down.pointwise_s2)
+        # chain_joins: conv3 of a block and conv1 of the next block of the same stage run as one kernel each way
+        # (ops.PointwiseJoinFunction, bitwise the same results); False keeps two kernels per join
+        self.chain_joins = bool(chain_joins)
+        self._join_next = [cur.joins(nxt) for cur, nxt in zip(blocks[:-1], blocks[1:])] + [False]
         self.avgpool, self.fc = net.avgpool, net.fc
 
     def forward(self, x):
         x = self.fstem(x) if self.fstem is not None else self.maxpool(self.stem(x))
-        x = self.layers(x)
+        blocks, h1 = list(self.layers), None
+        for i, blk in enumerate(blocks):
+            x = blk(x, h1=h1, nxt=blocks[i + 1] if self.chain_joins and self._join_next[i] else None)
+            h1 = None
+            if isinstance(x, _Joined):
+                x, h1 = x.out, x.h1
         if isinstance(x, tuple):
             x = x[0]
         if self.head32 is not None and self.head32_on:

@@ -48,7 +48,9 @@ extern "C" {
  * adil_grad can leave the reduction of those slabs to its consumer (`nslabs_out`); adil_adamw_l1ball consumes them.
  * 7: adil_zstep_codes — the z-step of a DDrague iteration also produces the next iteration's codes (as slabs); the
  * persistent fp8 copy of the dictionary (adil_dict_to_fp8, adil_adamw_clamp_fp8, adil_synth_fp8_packed).  8: 8-bit image
- * stores — ADIL_U8 as a source of adil_gather_images, adil_images_to_u8, adil_synth_store. */
+ * stores — ADIL_U8 as a source of adil_gather_images, adil_images_to_u8, adil_synth_store.  adil_pw_join_fwd /
+ * adil_pw_join_bwd were added under 8: new symbols only, no existing signature changed, and a library without them
+ * fails to load by name. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -301,6 +303,23 @@ int adil_pw_conv_fwd(const void* x, const void* w, const float* scale, const flo
 int adil_pw_conv_bwd(const void* g, const void* g2, const void* y, const float* scale, const void* wt, void* gx, void* gres,
                      int M, int K, int N, int relu, const void* xin, const float* pscale, const float* pshift, const void* g3,
                      int sub_w, int sub_hw, void* stream);
+
+/* Residual join of two consecutive bottlenecks of one stage (conv3 of block i-1 and conv1 of block i) as ONE kernel;
+ * the C-channel tensor between the two GEMMs is kept on chip.  W = width in {64, 128}, C = 4 W, M = pixels; bf16
+ * channels_last storage; w3 [C][W], w1 [W][C].  The results are bitwise those of
+ *     adil_pw_conv_fwd(h2raw, w3, scale3, shift3, res, out, M, W, C, 1, pscale2, pshift2, 0, 0)      (conv3, block i-1)
+ *     adil_pw_conv_fwd(out, w1, scale1, shift1, NULL, h1, M, C, W, 1, NULL, NULL, 0, 0)              (conv1, block i)
+ * Any other W: ADIL_EINVAL (the caller keeps the two calls). */
+int adil_pw_join_fwd(const void* h2raw, const float* pscale2, const float* pshift2, const void* w3, const float* scale3,
+                     const float* shift3, const void* res, void* out, const void* w1, const float* scale1,
+                     const float* shift1, void* h1, int M, int W, int C, void* stream);
+/* Input gradient of adil_pw_join_fwd, bitwise that of (t [M][C] is never written)
+ *     adil_pw_conv_bwd(g_h1, NULL, h1, scale1, wt1, t, NULL, M, C, W, 1, NULL, NULL, NULL, NULL, 0, 0)
+ *     adil_pw_conv_bwd(t, g_out, out, scale3, wt3, gx, gres, M, W, C, 1, h2raw, pscale2, pshift2, NULL, 0, 0)
+ * with the transposed weights wt1 [C][W] (of w1) and wt3 [W][C] (of w3); gres = gradient of res, gx = of h2raw. */
+int adil_pw_join_bwd(const void* g_h1, const void* h1, const float* scale1, const void* wt1, const void* g_out,
+                     const void* out, const float* scale3, void* gres, const void* wt3, const void* h2raw,
+                     const float* pscale2, const float* pshift2, void* gx, int M, int W, int C, void* stream);
 
 /* 3x3 / stride 1 / pad 1 convolution of the frozen network on channels_last storage, raw bf16 output (its BatchNorm +
  * ReLU run in the next pointwise kernel's prologue):  y[B][H][W][N] = conv3x3(x[B][H][W][C]; wp), weights packed
