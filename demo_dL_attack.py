@@ -62,6 +62,9 @@ def build_parser():
     p.add_argument('--fast-classifier', type=int, default=1,
                    help='bf16 ResNets: run the frozen classifier on the hand-written stem / pointwise / 3x3 kernels '
                         '(zoo.FusedResNet, same function up to bf16 rounding); 0 = plain PyTorch modules')
+    p.add_argument('--own-strided-conv', type=int, default=0, choices=[0, 1],
+                   help='with --fast-classifier: 1 = the stride-2 3x3 convolutions of the ResNet run in the hand-written '
+                        'kernel too (no library convolution is left in the classifier); 0 (default) = the library')
     return p
 
 
@@ -123,7 +126,8 @@ def main(args):
         weights = _fitted_weights(model_name, args.seed, train_dataset, n_classes, device)
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
                                  channels_last=fast, fuse_bn_act=fast, fuse_stem=fast,
-                                 head_fp32="inference" if fast else False)      # fp32 logits inside the DDrague inference loop
+                                 head_fp32="inference" if fast else False,      # fp32 logits inside the DDrague inference loop
+                                 own_strided_conv=fast and bool(args.own_strided_conv))
     if args.clean_accuracy:                                                               # demo_dL_attack.py:65-66
         from model_accuracy import model_accuracy, model_accuracy_distributed
         dataset.indexed = False

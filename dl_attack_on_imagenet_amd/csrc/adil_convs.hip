@@ -958,3 +958,260 @@ extern "C" int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H
     if (N % 128 == 0) return launch_conv3x3<128, 2>(x, wp, y, (int)M, H, W, C, N, (hipStream_t)stream);
     return launch_conv3x3<64, 4>(x, wp, y, (int)M, H, W, C, N, (hipStream_t)stream);   // 64 px x 64 ch wave tiles as well
 }
+
+// =========================================================================================================== //
+// 3x3 / stride 2 / pad 1 convolution of the frozen ResNet (conv2 of the first bottleneck of stages 2-4; conv1 of the
+// same BasicBlocks), NHWC bf16, raw output, forward AND input gradient, even H and W.  Both are a sum of tap-GEMMs
+// over rows r = (b, i, j) of the OH x OW = H/2 x W/2 grid:
+//   forward    y[r][n]  = sum_{kh,kw,c} x[(b, 2i-1+kh, 2j-1+kw)][c] * wp[n][kh*3+kw][c]      (9 taps; only kh = 0 at
+//              i = 0 and kw = 0 at j = 0 leave the image: H, W even).  Centre tap = input pixel 4r - 2j.
+//   gradient   input pixels fall into four parity classes (ph, pw) = (h & 1, w & 1); pixel (2i+ph, 2j+pw) receives
+//              gx[(b, 2i+ph, 2j+pw)][c] = sum_{kh in KH(ph), kw in KW(pw), n} g[(b, i + [kh = 0], j + [kw = 0])][n] * wpb[c][kh*3+kw][n]
+//              with KH(0) = {1}, KH(1) = {0, 2} (same for kw): 1 / 2 / 2 / 4 live taps, 9 tap-GEMMs per 2x2 block — the
+//              forward's FLOP count; no zero-upsampled g exists anywhere.  A workgroup owns 128 rows r and runs the four
+//              classes one after the other (every workgroup does the same 9 tap-GEMMs; the g rows stay in L2), writing
+//              input pixels 4r - 2j + ph*W + pw class by class.
+// One kernel does both: per (64-channel chunk, tap) the 128 source rows of the tap are gathered from global memory
+// (rows of a tap that leaves the image are zeroed on the way to LDS) next to the [BN][64] weight tile; both tiles are
+// double buffered in LDS with the next three pairs in registers or in flight (across class boundaries too), one barrier
+// per tap, 16 MFMAs per wave on 64 px x 64 (32) channel wave tiles as in conv3x3_kernel; a finished class leaves through
+// the idle buffer.  No zero-fill launch, no atomics: bitwise reproducible.
+// =========================================================================================================== //
+namespace {
+
+#define S2_BM 128
+
+template <int BN, bool BWD>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv3x3_s2_kernel(
+    const bf16_t* __restrict__ src, const bf16_t* __restrict__ wp, bf16_t* __restrict__ dst, int M, int OH, int OW, int K,
+    int NO, int MT, int NT) {
+    constexpr int CTW = BN / 64;                         // channel tiles per wave (2 x 2 waves: 64 px x BN/2 channels)
+    constexpr int XCH = S2_BM * 8 / 256;                 // 16-byte chunks of a source tile per thread (4)
+    constexpr int WCH = BN * 8 / 256;                    // ... of a weight tile
+    constexpr int OS = BN + 8;
+    constexpr int PAIR = (S2_BM + BN) * C3_LS;           // one buffer: source tile [128][C3_LS] | weight tile [BN][C3_LS]
+    constexpr int NCLS = BWD ? 4 : 1;
+    static_assert(S2_BM * OS <= PAIR, "the output transpose goes through one idle buffer");
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    bf16_t* sb = reinterpret_cast<bf16_t*>(smem_raw);    // [2][PAIR]
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
+    const int wpx = w & 1, wch = w >> 1;
+    int mt, nt;
+    if ((MT & 7) == 0) {                                 // the workgroups of one row tile go to ONE XCD (see pw_conv_fwd_kernel)
+        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
+        nt = j % NT;
+        mt = (j / NT) * 8 + xcd;
+    } else {
+        nt = blockIdx.x % NT;
+        mt = blockIdx.x / NT;
+    }
+    const int m0 = mt * S2_BM, n0 = nt * BN;
+    const int nci = K >> 6;
+    const int nit = nci * 9;                             // forward: 9 taps; gradient: 4 + 2 + 2 + 1 taps of the four classes
+    // gradient classes in the order (ph, pw) = (1,1) (1,0) (0,1) (0,0); taps per direction
+    auto cls_ph = [](int cls) { return BWD ? (cls < 2 ? 1 : 0) : 0; };
+    auto cls_pw = [](int cls) { return BWD ? ((cls & 1) ? 0 : 1) : 0; };
+
+    // the rows this thread stages: centre source row and which of its taps stay inside the image
+    int ctr[XCH];
+    unsigned flg[XCH];                                   // bit 0: row < M, bit 1: kh = 0 is inside, bit 2: kw = 0 is inside
+#pragma unroll
+    for (int i = 0; i < XCH; ++i) {
+        const int r = m0 + (tid >> 3) + 32 * i;
+        const int rc = r < M ? r : M - 1;
+        const int j = rc % OW, ii = (rc / OW) % OH;
+        ctr[i] = BWD ? rc : 4 * rc - 2 * j;
+        const bool okh = BWD ? (ii + 1 < OH) : (ii > 0), okw = BWD ? (j + 1 < OW) : (j > 0);
+        flg[i] = (r < M ? 1u : 0u) | (okh ? 2u : 0u) | (okw ? 4u : 0u);
+    }
+    // a (source, weight) tile pair on its way to LDS; three are in flight: tile it+3 is requested while tile it is
+    // multiplied (an L2 round trip is several times the 16 MFMAs of one tap, see conv3x3_kernel)
+    struct Tile {
+        u32x4 x[XCH], w[WCH];
+        unsigned ok;                                     // bit i: chunk i of x is real data (else a tap outside the image)
+    };
+    // (class, channel chunk, tap row, tap column) of the NEXT load_tiles call: tiles are requested in the order they
+    // are multiplied, class after class
+    int lcls = 0, lcc = 0, la = 0, lb = 0;
+    int lph = cls_ph(0), lpw = cls_pw(0), lnth = BWD ? 1 + lph : 3, lntw = BWD ? 1 + lpw : 3;
+    auto load_tiles = [&](Tile& t) {
+        const int kh = BWD ? (lph ? 2 * la : 1) : la, kw = BWD ? (lpw ? 2 * lb : 1) : lb;
+        const int off = BWD ? (kh == 0 ? OW : 0) + (kw == 0 ? 1 : 0) : (kh - 1) * 2 * OW + (kw - 1);
+        const unsigned need = 1u | (kh == 0 ? 2u : 0u) | (kw == 0 ? 4u : 0u);
+        unsigned okm = 0;
+#pragma unroll
+        for (int i = 0; i < XCH; ++i) {
+            const int ch = tid & 7;
+            const bool ok = (flg[i] & need) == need;
+            okm |= ok ? (1u << i) : 0u;
+            const int srow = ok ? ctr[i] + off : ctr[i];                     // always a valid address
+            t.x[i] = *reinterpret_cast<const u32x4*>(src + (size_t)srow * K + lcc * 64 + ch * 8);
+        }
+        t.ok = okm;
+#pragma unroll
+        for (int i = 0; i < WCH; ++i) {
+            const int q = tid + 256 * i, row = q >> 3, ch = q & 7;
+            t.w[i] = *reinterpret_cast<const u32x4*>(wp + ((size_t)(n0 + row) * 9 + kh * 3 + kw) * K + lcc * 64 + ch * 8);
+        }
+        if (++lb == lntw) {
+            lb = 0;
+            if (++la == lnth) {
+                la = 0;
+                if (++lcc == nci && lcls + 1 < NCLS) {
+                    lcc = 0;
+                    ++lcls;
+                    lph = cls_ph(lcls);
+                    lpw = cls_pw(lcls);
+                    lnth = 1 + lph;
+                    lntw = 1 + lpw;
+                }
+            }
+        }
+    };
+    auto store_tiles = [&](int buf, const Tile& t) {
+        bf16_t* sx = sb + buf * PAIR;
+        bf16_t* sw = sx + S2_BM * C3_LS;
+#pragma unroll
+        for (int i = 0; i < XCH; ++i) {
+            const int row = (tid >> 3) + 32 * i, ch = tid & 7;
+            u32x4 v = t.x[i];
+            const bool ok = (t.ok >> i) & 1u;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) v[j] = ok ? v[j] : 0u;
+            *reinterpret_cast<u32x4*>(sx + row * C3_LS + ch * 8) = v;
+        }
+#pragma unroll
+        for (int i = 0; i < WCH; ++i) {
+            const int q = tid + 256 * i, row = q >> 3, ch = q & 7;
+            *reinterpret_cast<u32x4*>(sw + row * C3_LS + ch * 8) = t.w[i];
+        }
+    };
+
+    f32x16 acc[2][CTW];
+    auto zero_acc = [&]() {
+#pragma unroll
+        for (int p = 0; p < 2; ++p)
+#pragma unroll
+            for (int ct = 0; ct < CTW; ++ct)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[p][ct][r] = 0.0f;
+    };
+    zero_acc();
+    // a finished class (the forward's only one): transpose through the idle buffer (all waves share one [128][OS]
+    // tile), 16-byte NHWC stores.  The tiles of the next class stay in flight in registers meanwhile.
+    auto finish_class = [&](int cls, bf16_t* so) {
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const int pl = wpx * 64 + p * 32 + c;
+#pragma unroll
+            for (int ct = 0; ct < CTW; ++ct) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    u32x2 t;
+                    t[0] = pack2_bf16(acc[p][ct][4 * q], acc[p][ct][4 * q + 1]);
+                    t[1] = pack2_bf16(acc[p][ct][4 * q + 2], acc[p][ct][4 * q + 3]);
+                    *reinterpret_cast<u32x2*>(so + pl * OS + (wch * CTW + ct) * 32 + 8 * q + 4 * h) = t;
+                }
+            }
+        }
+        lds_barrier();
+        const int ph = cls_ph(cls), pw = cls_pw(cls);
+        constexpr int CPP = BN / 8;
+#pragma unroll
+        for (int i = 0; i < S2_BM * CPP / 256; ++i) {
+            const int id = tid + 256 * i, px = id / CPP, ch = id - px * CPP;
+            const int r = m0 + px;
+            if (r < M) {
+                const size_t drow = BWD ? (size_t)(4 * r - 2 * (r % OW) + ph * 2 * OW + pw) : (size_t)r;
+                *reinterpret_cast<u32x4*>(dst + drow * NO + n0 + ch * 8) = *reinterpret_cast<const u32x4*>(so + px * OS + ch * 8);
+            }
+        }
+        lds_barrier();                                   // the buffer is free for the next tile
+        zero_acc();
+    };
+
+    int ccls = 0;                                        // the class being multiplied and the taps it has left
+    int crem = nci * (BWD ? 4 : 9);
+    auto tap_body = [&](int it, Tile& tfree, const Tile& tnext) {
+        // on entry: LDS buffer it & 1 holds tile it, tnext holds tile it+1, the third register set tile it+2 (in
+        // flight), tfree's tile is already in LDS
+        const int buf = it & 1;
+        if (it + 3 < nit) load_tiles(tfree);
+        const bf16_t* bx = sb + buf * PAIR + (wpx * 64 + c) * C3_LS + 8 * h;
+        const bf16_t* bw = sb + buf * PAIR + (S2_BM + wch * CTW * 32 + c) * C3_LS + 8 * h;
+#pragma unroll
+        for (int ks = 0; ks < 4; ++ks) {
+            const bf16x8 b0 = lds8(bx + 16 * ks);
+            const bf16x8 b1 = lds8(bx + 32 * C3_LS + 16 * ks);
+#pragma unroll
+            for (int ct = 0; ct < CTW; ++ct) {
+                const bf16x8 a = lds8(bw + ct * 32 * C3_LS + 16 * ks);
+                mma16(acc[0][ct], a, b0);
+                mma16(acc[1][ct], a, b1);
+            }
+        }
+        // the other buffer was last read before the previous barrier: it takes the class's output transpose, then tile it+1
+        if (--crem == 0) {                               // uniform: every wave meets the same barriers
+            finish_class(ccls, sb + (buf ^ 1) * PAIR);
+            ++ccls;
+            crem = nci * (1 + cls_ph(ccls)) * (1 + cls_pw(ccls));
+        }
+        if (it + 1 < nit) store_tiles(buf ^ 1, tnext);
+        lds_barrier();
+    };
+
+    Tile t0, t1, t2;
+    load_tiles(t0);
+    load_tiles(t1);                                      // nit >= 9
+    load_tiles(t2);
+    store_tiles(0, t0);
+    lds_barrier();
+    for (int it = 0; it < nit; it += 3) {                // nit = 9 * nci: a multiple of 3
+        tap_body(it, t0, t1);
+        tap_body(it + 1, t1, t2);
+        tap_body(it + 2, t2, t0);
+    }
+}
+
+template <int BN, bool BWD>
+int launch_conv3x3_s2(const void* src, const void* wp, void* dst, int M, int OH, int OW, int K, int NO, hipStream_t st) {
+    const int MT = (M + S2_BM - 1) / S2_BM, NT = NO / BN;
+    const size_t lds = (size_t)2 * (S2_BM + BN) * C3_LS * sizeof(bf16_t);
+    if (lds > 48 * 1024) {
+        const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_s2_kernel<BN, BWD>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL((conv3x3_s2_kernel<BN, BWD>), dim3((unsigned)(MT * NT)), dim3(256), lds, st,
+                       (const bf16_t*)src, (const bf16_t*)wp, (bf16_t*)dst, M, OH, OW, K, NO, MT, NT);
+    ADIL_CHECK_LAUNCH();
+    return 0;
+}
+
+// what both entry points cover; M = rows of the stride-2 grid
+bool conv3x3_s2_covers(int B, int H, int W, int C, int N, int* M) {
+    if (B <= 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0 || (H & 1) || (W & 1) || (C % 64) || (N % 64) || W > ADIL_CONV3X3_S2_MAX_W)
+        return false;
+    const long long m4 = (long long)B * H * W;           // rows of the full grid: every index is an int
+    if (m4 > 0x7fffffffLL) return false;
+    *M = (int)(m4 / 4);
+    return true;
+}
+
+}  // namespace
+
+extern "C" int adil_conv3x3_s2_fwd(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream) {
+    ADIL_ENTER();
+    int M = 0;
+    if (!x || !wp || !y || !conv3x3_s2_covers(B, H, W, C, N, &M)) return ADIL_EINVAL;
+    if (N % 128 == 0) return launch_conv3x3_s2<128, false>(x, wp, y, M, H / 2, W / 2, C, N, (hipStream_t)stream);
+    return launch_conv3x3_s2<64, false>(x, wp, y, M, H / 2, W / 2, C, N, (hipStream_t)stream);
+}
+
+extern "C" int adil_conv3x3_s2_bwd(const void* g, const void* wp_bwd, void* gx, int B, int H, int W, int C, int N, void* stream) {
+    ADIL_ENTER();
+    int M = 0;
+    if (!g || !wp_bwd || !gx || !conv3x3_s2_covers(B, H, W, C, N, &M)) return ADIL_EINVAL;
+    if (C % 128 == 0) return launch_conv3x3_s2<128, true>(g, wp_bwd, gx, M, H / 2, W / 2, N, C, (hipStream_t)stream);
+    return launch_conv3x3_s2<64, true>(g, wp_bwd, gx, M, H / 2, W / 2, N, C, (hipStream_t)stream);
+}

@@ -957,6 +957,70 @@ def conv3x3(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
     return Conv3x3Function.apply(x, wp_fwd, wp_bwd)
 
 
+CONV3X3_S2_MAX_W = 63        # ADIL_CONV3X3_S2_MAX_W of include/adil_hip.h
+
+
+def pack_conv3x3_s2_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
+    """(N,C,3,3) conv weight -> the two bf16 layouts of adil_conv3x3_s2_fwd / _bwd (include/adil_hip.h), both 2-D:
+    forward [N][9*C] (w[n][c][kh][kw] at [n][kh*3+kw][c], the layout of adil_conv3x3) and input gradient [C][9*N]
+    (w[n][c][kh][kw] at [c][kh*3+kw][n]: channels swapped, taps NOT flipped — the gradient kernel picks the live taps
+    of each pixel parity class by their forward index)."""
+    n, c, kh, kw = weight.shape
+    if (kh, kw) != (3, 3):
+        raise ValueError(f"expected a 3x3 convolution weight, got {tuple(weight.shape)}")
+    w = weight.detach().float()
+    fwd = w.permute(0, 2, 3, 1).reshape(n, 9 * c).to(torch.bfloat16).contiguous()
+    bwd = w.permute(1, 2, 3, 0).reshape(c, 9 * n).to(torch.bfloat16).contiguous()
+    return fwd, bwd
+
+
+def conv3x3_s2_covers(x: Tensor, cin: int, cout: int) -> bool:
+    """What adil_conv3x3_s2_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == cin and cin % 64 == 0
+            and cout % 64 == 0 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and 0 < x.shape[3] <= CONV3X3_S2_MAX_W
+            and x.shape[2] > 0 and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+
+
+class Conv3x3S2Function(torch.autograd.Function):
+    """3x3 / stride 2 / pad 1 convolution on channels_last bf16 tensors, raw output (adil_conv3x3_s2_fwd), and its input
+    gradient by pixel parity classes (adil_conv3x3_s2_bwd).  No weight gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, wp_fwd, wp_bwd):
+        lib = _lib.load()
+        b, c, h, w = x.shape
+        n = wp_fwd.shape[0]
+        x2 = x.permute(0, 2, 3, 1)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        y = torch.empty((b, h // 2, w // 2, n), dtype=torch.bfloat16, device=x.device)
+        if b > 0:
+            _lib.check(lib.adil_conv3x3_s2_fwd(_ptr(x2), _ptr(wp_fwd), _ptr(y), b, h, w, c, n, _stream()),
+                       "adil_conv3x3_s2_fwd")
+        ctx.save_for_backward(wp_bwd)
+        ctx.meta = (c, h, w)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        (wp_bwd,) = ctx.saved_tensors
+        c, h, w = ctx.meta
+        g2 = g.permute(0, 2, 3, 1)
+        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
+            g2 = g2.to(torch.bfloat16).contiguous()
+        b, n = g2.shape[0], g2.shape[3]
+        gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
+        if b > 0:
+            _lib.check(lib.adil_conv3x3_s2_bwd(_ptr(g2), _ptr(wp_bwd), _ptr(gx), b, h, w, c, n, _stream()),
+                       "adil_conv3x3_s2_bwd")
+        return gx.permute(0, 3, 1, 2), None, None
+
+
+def conv3x3_s2(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
+    return Conv3x3S2Function.apply(x, wp_fwd, wp_bwd)
+
+
 # --------------------------------------------------------------------------- #
 def pack_stem_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
     """(64,3,7,7) conv weight -> the two bf16 layouts of include/adil_hip.h: w_fwd [64][7][8][4], w_bwd [4][49][64]."""

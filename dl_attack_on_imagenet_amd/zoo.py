@@ -649,12 +649,31 @@ class _ConvAffine(_Fp32Tables):
             wp_fwd, wp_bwd = ops.pack_conv3x3_weights(conv.weight)
             self.register_buffer('wp_fwd', wp_fwd)
             self.register_buffer('wp_bwd', wp_bwd)
+        # the stride-2 3x3 layers (conv2 of the first bottleneck of stages 2-4, conv1 of the same BasicBlocks)
+        self.dense3x3_s2 = (conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1)
+                            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
+                            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0)
+        self.own_strided_conv = False    # set by use_own_strided_conv_ (FusedResNet(own_strided_conv=True))
+
+    def use_own_strided_conv_(self):
+        """Route a dense stride-2 3x3 layer to ops.conv3x3_s2 where the kernel covers the input (weights packed once)."""
+        if self.dense3x3_s2 and not self.own_strided_conv:
+            from . import ops
+            wp_fwd, wp_bwd = ops.pack_conv3x3_s2_weights(self.conv.weight)
+            self.register_buffer('wp_s2_fwd', wp_fwd.to(self.conv.weight.device))
+            self.register_buffer('wp_s2_bwd', wp_bwd.to(self.conv.weight.device))
+            self.own_strided_conv = True
+        return self
 
     def raw_conv(self, x):
-        """The convolution alone (no BatchNorm / ReLU): the hand-written 3x3 kernel where it applies, else the library."""
+        """The convolution alone (no BatchNorm / ReLU): the hand-written 3x3 kernels where they apply, else the library."""
         if self.dense3x3 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] <= 63:   # kernel limit: W <= 63
             from . import ops
             return ops.conv3x3(x, self.wp_fwd, self.wp_bwd)
+        if self.own_strided_conv and self.wp_s2_fwd.dtype == torch.bfloat16:
+            from . import ops
+            if ops.conv3x3_s2_covers(x, self.conv.in_channels, self.conv.out_channels):
+                return ops.conv3x3_s2(x, self.wp_s2_fwd, self.wp_s2_bwd)
         return self.conv(x)
 
     def _conv(self, x):
@@ -705,6 +724,7 @@ class _FusedResBlock(nn.Module):
             self.c2 = _ConvAffine(block.conv2, block.bn2, True)          # + residual, then ReLU
         self.down = None if block.downsample is None else _ConvAffine(block.downsample[0], block.downsample[1], False)
         self.emit_sub = False            # set by FusedResNet: the NEXT block has a stride-2 pointwise downsample
+        self.own_strided_conv = False    # set by FusedResNet(own_strided_conv=True)
 
     def joins(self, nxt) -> bool:
         """This block's conv3 and `nxt`'s conv1 can run as one residual-join kernel (ops.PointwiseJoinFunction): two
@@ -726,6 +746,10 @@ class _FusedResBlock(nn.Module):
             idt = xs
         elif xsub is not None and self.down.fused_pointwise_s2(xsub):
             idt = self.down(xsub, strided_view=True)
+        elif self.own_strided_conv and self.down.fused_pointwise_s2(xs) and xs.shape[2] % 2 == 0 and xs.shape[3] % 2 == 0:
+            # BasicBlocks hand on no [:, :, ::2, ::2] view: take it here (autograd's slice backward zero-fills the full
+            # grid once per such block) so that the downsample runs in the gathering pointwise kernel
+            idt = self.down(xs[:, :, ::2, ::2], strided_view=True)
         else:
             idt = self.down(xs)
         out = self.c1(xm) if h1 is None else h1
@@ -812,9 +836,13 @@ class FusedResNet(nn.Module):
     classifier calls (engine.precise_head): the logits' precision matters where the attack works next to the decision
     boundary — at inference on held-out images (+1.5 pp ASR over five paired dictionaries, most on the bad ones, at no
     cost) — while dictionaries LEARNED against the fp32 head came out consistently a little worse than those learned
-    against the bf16 head (profiles/r04_asr_gap.md)."""
+    against the bf16 head (profiles/r04_asr_gap.md).
+    `own_strided_conv`: the stride-2 3x3 convolutions run in the hand-written kernel (`ops.conv3x3_s2`) where it covers the
+    input (even H, W <= 63) and a BasicBlock's stride-2 downsample in the gathering pointwise kernel; with the fused stem
+    no library convolution is left and forward + input gradient are bitwise reproducible.  Off (default): the library,
+    every launch as before (profiles/conv_s2_bench.json, profiles/conv_s2_asr.md)."""
 
-    def __init__(self, net: ResNet, normalize=None, head_fp32=False, chain_joins=True):
+    def __init__(self, net: ResNet, normalize=None, head_fp32=False, chain_joins=True, own_strided_conv=False):
         super().__init__()
         if head_fp32 not in (False, True, "inference"):
             raise ValueError("head_fp32 must be False, True or 'inference'")
@@ -837,6 +865,15 @@ class FusedResNet(nn.Module):
         self.chain_joins = bool(chain_joins)
         self._join_next = [cur.joins(nxt) for cur, nxt in zip(blocks[:-1], blocks[1:])] + [False]
         self.avgpool, self.fc = net.avgpool, net.fc
+        # own_strided_conv: the stride-2 3x3 convolutions run in ops.conv3x3_s2 and the BasicBlock downsamples in the
+        # gathering pointwise kernel, so that (with the fused stem) no library convolution is left; off: the library
+        self.own_strided_conv = bool(own_strided_conv)
+        if self.own_strided_conv:
+            for blk in blocks:
+                blk.own_strided_conv = True
+                for m in blk.children():
+                    if isinstance(m, _ConvAffine):
+                        m.use_own_strided_conv_()
 
     def forward(self, x):
         x = self.fstem(x) if self.fstem is not None else self.maxpool(self.stem(x))
@@ -903,15 +940,18 @@ def fit_centroid_head(model: nn.Module, images: torch.Tensor, labels: torch.Tens
 def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights: Optional[str] = None,
                      device=None, dtype: torch.dtype = torch.float32, channels_last: bool = False,
                      fold_bn: bool = False, pad_input_channels: int = 0, fuse_bn_act: bool = False,
-                     fuse_stem: bool = False, head_fp32=False) -> nn.Module:
+                     fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
     normalisation and the first stage into the stem kernels (the Sequential then holds the network alone); head_fp32
     (with fuse_bn_act) keeps global pooling + the last linear layer in fp32 under a bf16 cast (fp32 logits): True = always,
-    "inference" = only inside engine.precise_head (the DDrague inference solver), see FusedResNet."""
+    "inference" = only inside engine.precise_head (the DDrague inference solver), see FusedResNet; own_strided_conv (with
+    fuse_bn_act) runs the stride-2 3x3 convolutions in the hand-written kernel instead of the library (off by default)."""
     if head_fp32 and not fuse_bn_act:
         raise ValueError("head_fp32 is a switch of the FusedResNet path (fuse_bn_act=True)")
+    if own_strided_conv and not fuse_bn_act:
+        raise ValueError("own_strided_conv is a switch of the FusedResNet path (fuse_bn_act=True)")
     key = canonical_name(name)
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
@@ -926,7 +966,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         stem_fused = bool(fuse_stem)
         if stem_fused and dtype != torch.bfloat16:
             raise ValueError("fuse_stem needs a bfloat16 network (the stem kernels produce bf16 activations)")
-        net = FusedResNet(net, normalize=(mean, std) if stem_fused else None, head_fp32=head_fp32)
+        net = FusedResNet(net, normalize=(mean, std) if stem_fused else None, head_fp32=head_fp32,
+                          own_strided_conv=own_strided_conv)
     elif fold_bn:
         fold_batchnorm_(net)
     model = nn.Sequential(net) if stem_fused else nn.Sequential(Normalize(mean=mean, std=std), net)

@@ -49,8 +49,8 @@ extern "C" {
  * 7: adil_zstep_codes — the z-step of a DDrague iteration also produces the next iteration's codes (as slabs); the
  * persistent fp8 copy of the dictionary (adil_dict_to_fp8, adil_adamw_clamp_fp8, adil_synth_fp8_packed).  8: 8-bit image
  * stores — ADIL_U8 as a source of adil_gather_images, adil_images_to_u8, adil_synth_store.  adil_pw_join_fwd /
- * adil_pw_join_bwd were added under 8: new symbols only, no existing signature changed, and a library without them
- * fails to load by name. */
+ * adil_pw_join_bwd, and after them adil_conv3x3_s2_fwd / adil_conv3x3_s2_bwd, were added under 8: new symbols only, no
+ * existing signature changed, and a library without them fails to load by name. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -326,6 +326,22 @@ int adil_pw_join_bwd(const void* g_h1, const void* h1, const float* scale1, cons
  * wp[N][9][C] = w[n][c][kh][kw] at [n][kh*3+kw][c].  The input gradient is the same call on wp' [C][9][N] =
  * w[n][c][2-kh][2-kw] at [c][kh*3+kw][n].  C % 64 == 0, N % 64 == 0, W <= 63. */
 int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream);
+
+/* 3x3 / stride 2 / pad 1 convolution of the frozen network on channels_last storage (conv2 of the first bottleneck of
+ * stages 2-4, conv1 of the same BasicBlocks), raw bf16 output, bf16 MFMA with fp32 accumulation, one rounding.
+ * H, W are the INPUT grid in both calls (even), the stride-2 grid is OH x OW = H/2 x W/2:
+ *   adil_conv3x3_s2_fwd : y[B][OH][OW][N] = sum x[b][2oh-1+kh][2ow-1+kw][c] * w[n][c][kh][kw],  x is [B][H][W][C],
+ *                         weights packed as for adil_conv3x3: wp[N][9][C] = w[n][c][kh][kw] at [n][kh*3+kw][c]
+ *   adil_conv3x3_s2_bwd : gx[B][H][W][C] = sum g[b][(h+1-kh)/2][(w+1-kw)/2][n] * w[n][c][kh][kw] over the taps whose
+ *                         quotients are integers and in range (1 / 2 / 2 / 4 taps by the parity of (h, w); g is never
+ *                         zero-upsampled), g is [B][OH][OW][N], weights wp_bwd[C][9][N] = w[n][c][kh][kw] at
+ *                         [c][kh*3+kw][n] (taps NOT flipped, channels swapped).  Every element of gx is written.
+ * C % 64 == 0, N % 64 == 0 (C != N allowed), H and W even, W <= ADIL_CONV3X3_S2_MAX_W (the width limit of adil_conv3x3:
+ * image sizes whose stride-1 3x3 layers run here); anything else: ADIL_EINVAL before any launch, outputs untouched.
+ * No atomics: bitwise reproducible. */
+#define ADIL_CONV3X3_S2_MAX_W 63
+int adil_conv3x3_s2_fwd(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream);
+int adil_conv3x3_s2_bwd(const void* g, const void* wp_bwd, void* gx, int B, int H, int W, int C, int N, void* stream);
 
 #ifdef __cplusplus
 }
