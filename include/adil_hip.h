@@ -250,7 +250,14 @@ int adil_dict_rightmul(const float* d, const float* mat, int P, int K, float* ou
 int adil_image_metrics(const void* adv, const void* x, int B, int P, int dtype, float* sq_err, float* sq_norm,
                        void* stream);
 
-/* Frozen-classifier epilogues (NOT part of the ADiL maths; no reference counterpart — they replace the separate
+/* Precondition of the ReLU masks of adil_pw_conv_bwd and adil_pw_join_bwd: the tensor a mask [y > 0] is taken from (y, h1,
+ * out) must not hold -0.0.  Those two kernels test the sign of the 16-bit pattern, so -0.0 would count as positive.
+ * adil_pw_conv_fwd and adil_pw_join_fwd clip with an integer max on the bf16 pattern and write +0 also for a -0.0
+ * pre-activation (a negative scale times a zero accumulator plus a -0.0 shift: a row of
+ * tests/test_gpu_classifier_routes.py), so a y they produced qualifies.  adil_affine_act_bwd compares values (y > 0.0f) in
+ * both dtypes and has no such precondition.
+ *
+ * Frozen-classifier epilogues (NOT part of the ADiL maths; no reference counterpart — they replace the separate
  * BatchNorm(eval) / add / ReLU kernels PyTorch launches around each convolution of the frozen network, e.g. the
  * torchvision ResNet blocks the reference builds at demo_dL_attack.py:41-59):
  *     y = act( x * scale[c] + shift[c] (+ res) ),  act = ReLU if relu else identity
@@ -299,7 +306,9 @@ int adil_pw_conv_fwd(const void* x, const void* w, const float* scale, const flo
  * M = B*4*OH*OW): a gradient living on the stride-2 grid, [M/4][N]; pixel (n,h,w) receives g3[(n,h/2,w/2)] for even
  * h and w (the zero-upsampled tensor is never materialised).  N % 64 == 0, K % 64 == 0, N <= 2048.
  * With the forward's prologue (xin = the raw x, pscale, pshift) the result is the gradient wrt xin:
- *     gx *= [xin * pscale + pshift > 0] * pscale. */
+ *     gx *= [xin * pscale + pshift > 0] * pscale.
+ * This epilogue reads pscale / pshift from global memory, so unlike the forward's prologue it has no K <= 512 limit.
+ * y must not hold -0.0 (see "Precondition of the ReLU masks" above). */
 int adil_pw_conv_bwd(const void* g, const void* g2, const void* y, const float* scale, const void* wt, void* gx, void* gres,
                      int M, int K, int N, int relu, const void* xin, const float* pscale, const float* pshift, const void* g3,
                      int sub_w, int sub_hw, void* stream);
@@ -316,7 +325,8 @@ int adil_pw_join_fwd(const void* h2raw, const float* pscale2, const float* pshif
 /* Input gradient of adil_pw_join_fwd, bitwise that of (t [M][C] is never written)
  *     adil_pw_conv_bwd(g_h1, NULL, h1, scale1, wt1, t, NULL, M, C, W, 1, NULL, NULL, NULL, NULL, 0, 0)
  *     adil_pw_conv_bwd(t, g_out, out, scale3, wt3, gx, gres, M, W, C, 1, h2raw, pscale2, pshift2, NULL, 0, 0)
- * with the transposed weights wt1 [C][W] (of w1) and wt3 [W][C] (of w3); gres = gradient of res, gx = of h2raw. */
+ * with the transposed weights wt1 [C][W] (of w1) and wt3 [W][C] (of w3); gres = gradient of res, gx = of h2raw.
+ * h1 and out must not hold -0.0 (see "Precondition of the ReLU masks" above). */
 int adil_pw_join_bwd(const void* g_h1, const void* h1, const float* scale1, const void* wt1, const void* g_out,
                      const void* out, const float* scale3, void* gres, const void* wt3, const void* h2raw,
                      const float* pscale2, const float* pshift2, void* gx, int M, int W, int C, void* stream);
