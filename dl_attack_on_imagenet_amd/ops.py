@@ -1022,6 +1022,77 @@ def conv3x3_s2(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
 
 
 # --------------------------------------------------------------------------- #
+def pack_dw3x3_weights(conv_weight: Tensor, scale: Optional[Tensor] = None) -> Tensor:
+    """(C,1,3,3) depthwise conv weight -> the [9][C] fp32 table of adil_dw3x3_fwd / _bwd (include/adil_hip.h):
+    w[c][kh][kw] * scale[c] at [kh*3+kw][c], the product formed in fp64 and rounded once to fp32.  scale = the eval-BatchNorm
+    factor gamma / sqrt(var + eps) (any float dtype, used as fp64), None = 1."""
+    if conv_weight.dim() != 4 or tuple(conv_weight.shape[1:]) != (1, 3, 3):
+        raise ValueError(f"expected a depthwise 3x3 convolution weight (C,1,3,3), got {tuple(conv_weight.shape)}")
+    w = conv_weight.detach().double().reshape(conv_weight.shape[0], 9)
+    if scale is not None:
+        w = w * scale.detach().double().reshape(-1, 1).to(w.device)
+    return w.t().float().contiguous()
+
+
+def dw_conv3x3_covers(x: Tensor, C: int) -> bool:
+    """What adil_dw3x3_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == C and C > 0 and C % 8 == 0
+            and x.shape[2] > 0 and x.shape[3] > 0)
+
+
+class DepthwiseConv3x3Function(torch.autograd.Function):
+    """Depthwise 3x3 / pad 1 / stride 1|2 convolution + folded BatchNorm (+ ReLU6) on channels_last bf16 tensors
+    (adil_dw3x3_fwd); the input gradient gathers from the output grid and takes the ReLU6 mask from the saved output
+    (adil_dw3x3_bwd).  No weight gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, w9c, bias, stride, relu6):
+        lib = _lib.load()
+        b, c, h, w = x.shape
+        x2 = x.permute(0, 2, 3, 1)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
+        y = torch.empty((b, oh, ow, c), dtype=torch.bfloat16, device=x.device)
+        if b > 0:
+            _lib.check(lib.adil_dw3x3_fwd(_ptr(x2), _ptr(w9c), _ptr(bias), _ptr(y), b, h, w, c, int(stride), int(bool(relu6)),
+                                          _stream()), "adil_dw3x3_fwd")
+        ctx.save_for_backward(w9c, y if relu6 else None)
+        ctx.meta = (h, w, int(stride), int(bool(relu6)))
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        w9c, y = ctx.saved_tensors
+        h, w, stride, relu6 = ctx.meta
+        g2 = g.permute(0, 2, 3, 1)
+        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
+            g2 = g2.to(torch.bfloat16).contiguous()
+        b, c = g2.shape[0], g2.shape[3]
+        gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
+        if b > 0:
+            _lib.check(lib.adil_dw3x3_bwd(_ptr(g2), _ptr(y), _ptr(w9c), _ptr(gx), b, h, w, c, stride, relu6, _stream()),
+                       "adil_dw3x3_bwd")
+        return gx.permute(0, 3, 1, 2), None, None, None, None
+
+
+def dw_conv3x3(x: Tensor, w9c: Tensor, bias: Optional[Tensor], stride: int = 1, relu6: bool = True) -> Tensor:
+    """x (B,C,H,W) bf16 in channels_last memory format -> (B,C,OH,OW), same format, no copies."""
+    c = x.shape[1]
+    if not dw_conv3x3_covers(x, c):
+        raise ValueError(f"adil_dw3x3 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
+    if w9c.dtype != torch.float32 or tuple(w9c.shape) != (9, c) or not w9c.is_contiguous() or w9c.device != x.device:
+        raise ValueError(f"w9c must be a contiguous (9, {c}) float32 table on {x.device}")
+    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (c,) or not bias.is_contiguous()
+                             or bias.device != x.device):
+        raise ValueError(f"bias must be a contiguous ({c},) float32 table on {x.device}")
+    if stride not in (1, 2):
+        raise ValueError(f"stride must be 1 or 2, got {stride}")
+    return DepthwiseConv3x3Function.apply(x, w9c, bias, stride, relu6)
+
+
+# --------------------------------------------------------------------------- #
 def pack_stem_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
     """(64,3,7,7) conv weight -> the two bf16 layouts of include/adil_hip.h: w_fwd [64][7][8][4], w_bwd [4][49][64]."""
     if tuple(weight.shape) != (64, 3, 7, 7):

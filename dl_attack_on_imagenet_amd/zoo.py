@@ -626,6 +626,64 @@ class _Fp32Tables(nn.Module):
         return self
 
 
+class _OwnDepthwise(nn.Sequential):
+    """A `_ConvBNReLU6` whose convolution is depthwise 3x3 (pad 1, dilation 1, stride 1|2, groups == in == out), run as ONE
+    kernel pass (`ops.dw_conv3x3`: convolution, folded eval-BatchNorm and ReLU6) where the kernel covers the input.  The
+    original conv / bn / ReLU6 stay as submodules '0' / '1' / '2' (same state_dict keys; they serve every other input: CPU,
+    fp32, not channels_last).  The folded tables `w9c` [9][C] and `bias` [C] are derived in fp64 from the weights the block
+    holds when it is rewritten, kept fp32 under `.to(bfloat16)` like `_Fp32Tables`, follow device moves, and are not part
+    of the state_dict."""
+    _TABLES = ('w9c', 'bias')
+
+    def __init__(self, block: _ConvBNReLU6):
+        super().__init__(*block.children())
+        conv, bn = self[0], self[1]
+        if not _is_depthwise3x3(block):
+            raise ValueError("not a depthwise 3x3 conv + BatchNorm + ReLU6 block")
+        from . import ops
+        with torch.no_grad():            # the whole fold in fp64, one rounding to fp32 per table entry
+            scale64 = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+            shift = (bn.bias.double() - bn.running_mean.double() * scale64).float().contiguous()
+        self.channels, self.stride = conv.out_channels, conv.stride[0]
+        self.register_buffer('w9c', ops.pack_dw3x3_weights(conv.weight, scale64), persistent=False)
+        self.register_buffer('bias', shift, persistent=False)
+
+    def _apply(self, fn, recurse=True):
+        keep = {n: getattr(self, n) for n in self._TABLES}
+        super()._apply(fn, recurse)
+        for n, t in keep.items():
+            setattr(self, n, t.to(device=fn(t).device))
+        return self
+
+    def forward(self, x):
+        from . import ops
+        if (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and ops.dw_conv3x3_covers(x, self.channels)
+                and x.is_contiguous(memory_format=torch.channels_last) and self.w9c.device == x.device):
+            return ops.dw_conv3x3(x, self.w9c, self.bias, self.stride, True)
+        return super().forward(x)
+
+
+def _is_depthwise3x3(block) -> bool:
+    if not isinstance(block, _ConvBNReLU6) or len(block) != 3:
+        return False
+    conv, bn = block[0], block[1]
+    return (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and conv.kernel_size == (3, 3)
+            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.stride in ((1, 1), (2, 2))
+            and conv.groups == conv.in_channels == conv.out_channels and conv.bias is None
+            and conv.padding_mode == 'zeros')
+
+
+def use_own_depthwise_(net: nn.Module) -> int:
+    """Replace every depthwise 3x3 `_ConvBNReLU6` of the network by an `_OwnDepthwise`; returns how many were replaced."""
+    n = 0
+    for parent in list(net.modules()):
+        for name, child in list(parent._modules.items()):
+            if _is_depthwise3x3(child) and not isinstance(child, _OwnDepthwise):
+                parent._modules[name] = _OwnDepthwise(child)
+                n += 1
+    return n
+
+
 class _ConvAffine(_Fp32Tables):
     """conv (weights untouched) followed by the fused eval-BatchNorm [+ residual] [+ ReLU] epilogue kernel."""
 
@@ -940,19 +998,28 @@ def fit_centroid_head(model: nn.Module, images: torch.Tensor, labels: torch.Tens
 def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights: Optional[str] = None,
                      device=None, dtype: torch.dtype = torch.float32, channels_last: bool = False,
                      fold_bn: bool = False, pad_input_channels: int = 0, fuse_bn_act: bool = False,
-                     fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False) -> nn.Module:
+                     fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False,
+                     own_depthwise: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
     normalisation and the first stage into the stem kernels (the Sequential then holds the network alone); head_fp32
     (with fuse_bn_act) keeps global pooling + the last linear layer in fp32 under a bf16 cast (fp32 logits): True = always,
     "inference" = only inside engine.precise_head (the DDrague inference solver), see FusedResNet; own_strided_conv (with
-    fuse_bn_act) runs the stride-2 3x3 convolutions in the hand-written kernel instead of the library (off by default)."""
+    fuse_bn_act) runs the stride-2 3x3 convolutions in the hand-written kernel instead of the library (off by default);
+    own_depthwise (MobileNetV2, bf16, channels_last) runs the 17 depthwise 3x3 layers with their BatchNorm and ReLU6 in
+    the hand-written kernel (`_OwnDepthwise`; off by default)."""
     if head_fp32 and not fuse_bn_act:
         raise ValueError("head_fp32 is a switch of the FusedResNet path (fuse_bn_act=True)")
     if own_strided_conv and not fuse_bn_act:
         raise ValueError("own_strided_conv is a switch of the FusedResNet path (fuse_bn_act=True)")
     key = canonical_name(name)
+    if own_depthwise and key != 'mobilenet_v2':
+        raise ValueError("own_depthwise is a switch of MobileNetV2 (the depthwise 3x3 layers of no other network are covered)")
+    if own_depthwise and dtype != torch.bfloat16:
+        raise ValueError("own_depthwise needs a bfloat16 network (the depthwise kernels read and write bf16 activations)")
+    if own_depthwise and not channels_last:
+        raise ValueError("own_depthwise needs channels_last=True (the depthwise kernels work on channels_last storage)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -962,6 +1029,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     net.eval()
     mean, std = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
     stem_fused = False
+    if own_depthwise:                    # after the weights are loaded: the tables are folded from them
+        use_own_depthwise_(net)
     if fuse_bn_act and isinstance(net, ResNet):
         stem_fused = bool(fuse_stem)
         if stem_fused and dtype != torch.bfloat16:

@@ -50,7 +50,8 @@ extern "C" {
  * persistent fp8 copy of the dictionary (adil_dict_to_fp8, adil_adamw_clamp_fp8, adil_synth_fp8_packed).  8: 8-bit image
  * stores — ADIL_U8 as a source of adil_gather_images, adil_images_to_u8, adil_synth_store.  adil_pw_join_fwd /
  * adil_pw_join_bwd, and after them adil_conv3x3_s2_fwd / adil_conv3x3_s2_bwd, were added under 8: new symbols only, no
- * existing signature changed, and a library without them fails to load by name. */
+ * existing signature changed, and a library without them fails to load by name.  adil_dw3x3_fwd / adil_dw3x3_bwd joined them the
+ * same way. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -352,6 +353,27 @@ int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H, int W, in
 #define ADIL_CONV3X3_S2_MAX_W 63
 int adil_conv3x3_s2_fwd(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream);
 int adil_conv3x3_s2_bwd(const void* g, const void* wp_bwd, void* gx, int B, int H, int W, int C, int N, void* stream);
+
+/* Depthwise 3x3 / pad 1 / stride 1 or 2 convolution (groups == channels: the 17 such layers of MobileNetV2) of the frozen
+ * network on channels_last storage, with the layer's eval-BatchNorm folded into the weights and its ReLU6 applied in the
+ * same pass: bf16 in / out, fp32 arithmetic, ONE rounding to bf16 (nearest even).  H, W are the INPUT grid in both calls,
+ * any H, W >= 1 (odd sizes included); the output grid is OH x OW = (H-1)/stride + 1 x (W-1)/stride + 1.
+ *   w    [9][C] fp32 = w[c][kh][kw] * scale[c] at [kh*3+kw][c]   (scale = gamma / sqrt(var + eps), derived in fp64)
+ *   bias [C] fp32    = beta - mean * scale; may be NULL (no bias)
+ *   adil_dw3x3_fwd : y[b][oh][ow][c] = act( sum x[b][s oh-1+kh][s ow-1+kw][c] * w[kh*3+kw][c] + bias[c] ),  x is [B][H][W][C],
+ *                    act = min(max(., 0), 6) if relu6 else the identity
+ *   adil_dw3x3_bwd : gx[b][h][w][c] = sum (g m)[b][(h+1-kh)/s][(w+1-kw)/s][c] * w[kh*3+kw][c] over the taps whose quotients
+ *                    are integers and in range (g is never zero-upsampled), g and y are [B][OH][OW][C];
+ *                    m = [0 < y < 6] taken from the stored bf16 y by comparing VALUES (so -0.0 in y is simply a zero: no
+ *                    precondition, unlike adil_pw_conv_bwd); relu6 == 0: m = 1 and y may be NULL.
+ *                    Every element of gx is written.  Input gradient only: the network is frozen.
+ * C % 8 == 0 (16-byte lanes), 16-byte aligned pointers; anything else, a stride outside {1, 2}, a non-positive size or a NULL
+ * mandatory pointer: ADIL_EINVAL before any launch, outputs untouched.  Element offsets are 64-bit (B H W C may pass 2^31).
+ * No atomics: bitwise reproducible. */
+int adil_dw3x3_fwd(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C, int stride,
+                   int relu6, void* stream);
+int adil_dw3x3_bwd(const void* g, const void* y, const float* w, void* gx, int B, int H, int W, int C, int stride,
+                   int relu6, void* stream);
 
 #ifdef __cplusplus
 }
