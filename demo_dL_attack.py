@@ -68,6 +68,10 @@ def build_parser():
     p.add_argument('--own-depthwise', type=int, default=0, choices=[0, 1],
                    help='-m mobilenet --dtype bf16: 1 = the 17 depthwise 3x3 layers (with their BatchNorm and ReLU6) run in '
                         'the hand-written kernel on channels_last storage; 0 (default) = the library.  Ignored otherwise')
+    p.add_argument('--own-pointwise', type=int, default=0, choices=[0, 1],
+                   help='-m mobilenet --dtype bf16: 1 = the 34 1x1 layers (with their BatchNorm, ReLU6 and residual add) run '
+                        'in the narrow-channel GEMM kernel on channels_last storage; 0 (default) = the library.  Independent '
+                        'of --own-depthwise.  Ignored otherwise')
     return p
 
 
@@ -127,9 +131,11 @@ def main(args):
     weights = args.weights
     if structured and weights is None:
         weights = _fitted_weights(model_name, args.seed, train_dataset, n_classes, device)
-    own_dw = bool(args.own_depthwise) and dtype == torch.bfloat16 and zoo.canonical_name(model_name) == 'mobilenet_v2'
+    mobile_bf16 = dtype == torch.bfloat16 and zoo.canonical_name(model_name) == 'mobilenet_v2'
+    own_dw, own_pw = bool(args.own_depthwise) and mobile_bf16, bool(args.own_pointwise) and mobile_bf16
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
-                                 channels_last=fast or own_dw, own_depthwise=own_dw, fuse_bn_act=fast, fuse_stem=fast,
+                                 channels_last=fast or own_dw or own_pw, own_depthwise=own_dw, own_pointwise=own_pw, fuse_bn_act=fast,
+                                 fuse_stem=fast,
                                  head_fp32="inference" if fast else False,      # fp32 logits inside the DDrague inference loop
                                  own_strided_conv=fast and bool(args.own_strided_conv))
     if args.clean_accuracy:                                                               # demo_dL_attack.py:65-66

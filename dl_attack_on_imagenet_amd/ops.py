@@ -1093,6 +1093,79 @@ def dw_conv3x3(x: Tensor, w9c: Tensor, bias: Optional[Tensor], stride: int = 1, 
 
 
 # --------------------------------------------------------------------------- #
+def pw8_conv_covers(x: Tensor, cin: int, cout: int) -> bool:
+    """What adil_pw8_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
+    ok = lambda c: 8 <= c <= 2048 and c % 8 == 0
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == cin and ok(cin) and ok(cout)
+            and 1 <= x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+
+
+class Pointwise8Function(torch.autograd.Function):
+    """1x1 convolution + eval-BatchNorm (+ residual) (+ ReLU6) on channels_last bf16 tensors as one GEMM kernel
+    (adil_pw8_fwd); the input gradient takes the ReLU6 mask from the saved output (adil_pw8_bwd) and the residual input
+    receives the incoming gradient itself.  No weight gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, w2d, wt2d, scale, shift, res, relu6):
+        lib = _lib.load()
+        b, k, h, w = x.shape
+        n = w2d.shape[0]
+        x2 = x.permute(0, 2, 3, 1)
+        if not x2.is_contiguous():
+            x2 = x2.contiguous()
+        r2 = None
+        if res is not None:
+            r2 = res.permute(0, 2, 3, 1)
+            if not r2.is_contiguous():
+                r2 = r2.contiguous()
+        y = torch.empty((b, h, w, n), dtype=torch.bfloat16, device=x.device)
+        _lib.check(lib.adil_pw8_fwd(_ptr(x2), _ptr(w2d), _ptr(scale), _ptr(shift), _ptr(r2), _ptr(y), b * h * w, k, n,
+                                    int(bool(relu6)), _stream()), "adil_pw8_fwd")
+        ctx.save_for_backward(wt2d, scale, y if relu6 else None)
+        ctx.meta = (k, n, int(bool(relu6)), res is not None)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        wt2d, scale, y = ctx.saved_tensors
+        k, n, relu6, has_res = ctx.meta
+        g2 = g.permute(0, 2, 3, 1)
+        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
+            g2 = g2.to(torch.bfloat16).contiguous()
+        b, h, w = g2.shape[0], g2.shape[1], g2.shape[2]
+        gx = None
+        if ctx.needs_input_grad[0]:
+            gx = torch.empty((b, h, w, k), dtype=torch.bfloat16, device=g2.device)
+            _lib.check(lib.adil_pw8_bwd(_ptr(g2), _ptr(y), _ptr(scale), _ptr(wt2d), _ptr(gx), b * h * w, k, n, relu6, _stream()),
+                       "adil_pw8_bwd")
+            gx = gx.permute(0, 3, 1, 2)
+        return gx, None, None, None, None, (g if has_res and ctx.needs_input_grad[5] else None), None
+
+
+def pw8_conv(x: Tensor, w2d: Tensor, wt2d: Tensor, scale: Tensor, shift: Tensor, res: Optional[Tensor] = None,
+             relu6: bool = False) -> Tensor:
+    """x (B,K,H,W) bf16 in channels_last memory format -> act((x . w2d^T) * scale + shift (+ res)) as (B,N,H,W), same
+    format, no copies.  w2d (N,K) and its transpose wt2d (K,N) bf16, scale / shift (N,) fp32, res (B,N,H,W) only without
+    relu6."""
+    if w2d.dim() != 2:
+        raise ValueError(f"w2d must be a (N, K) matrix, got {tuple(w2d.shape)}")
+    n, k = w2d.shape
+    if not pw8_conv_covers(x, k, n):
+        raise ValueError(f"adil_pw8 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with a {n} x {k} weight")
+    for name, t, shape, dt in (("w2d", w2d, (n, k), torch.bfloat16), ("wt2d", wt2d, (k, n), torch.bfloat16),
+                               ("scale", scale, (n,), torch.float32), ("shift", shift, (n,), torch.float32)):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"{name} must be a contiguous {shape} {dt} tensor on {x.device}")
+    if res is not None:
+        if relu6:
+            raise ValueError("a residual input goes with the linear bottleneck only (relu6=False)")
+        if res.dtype != torch.bfloat16 or res.device != x.device or tuple(res.shape) != (x.shape[0], n, x.shape[2], x.shape[3]):
+            raise ValueError(f"res must be a bf16 {(x.shape[0], n, x.shape[2], x.shape[3])} tensor on {x.device}")
+    return Pointwise8Function.apply(x, w2d, wt2d, scale, shift, res, bool(relu6))
+
+
+# --------------------------------------------------------------------------- #
 def pack_stem_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
     """(64,3,7,7) conv weight -> the two bf16 layouts of include/adil_hip.h: w_fwd [64][7][8][4], w_bwd [4][49][64]."""
     if tuple(weight.shape) != (64, 3, 7, 7):

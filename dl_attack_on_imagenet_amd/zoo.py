@@ -684,6 +684,115 @@ def use_own_depthwise_(net: nn.Module) -> int:
     return n
 
 
+def _is_pointwise(conv, bn) -> bool:
+    return (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and conv.kernel_size == (1, 1)
+            and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1
+            and conv.bias is None and conv.in_channels % 8 == 0 and conv.out_channels % 8 == 0
+            and 8 <= conv.in_channels <= 2048 and 8 <= conv.out_channels <= 2048)
+
+
+def _is_pointwise_block(block) -> bool:
+    return isinstance(block, _ConvBNReLU6) and len(block) == 3 and _is_pointwise(block[0], block[1])
+
+
+class _Pw8Tables(nn.Module):
+    """What `ops.pw8_conv` needs of one 1x1 convolution + eval-BatchNorm, as non-persistent buffers (no state_dict
+    entries): `scale` / `shift` [N], derived in fp64 as `_bn_affine` derives them and kept fp32 under `.to(bfloat16)`;
+    `wt2d` [K][N], the transposed weight, which is cast with the network (its bf16 rounding is the weight's own).  The
+    [N][K] weight is the convolution's own storage."""
+    _TABLES = ('scale', 'shift')
+
+    def _init_tables(self, conv, bn):
+        scale, shift = _bn_affine(bn)
+        self.cin, self.cout = conv.in_channels, conv.out_channels
+        self.register_buffer('scale', scale, persistent=False)
+        self.register_buffer('shift', shift, persistent=False)
+        self.register_buffer('wt2d', conv.weight.detach().reshape(self.cout, self.cin).t().contiguous(), persistent=False)
+
+    def _apply(self, fn, recurse=True):
+        keep = {n: getattr(self, n) for n in self._TABLES}
+        super()._apply(fn, recurse)
+        for n, t in keep.items():
+            setattr(self, n, t.to(device=fn(t).device))
+        return self
+
+    def _covers(self, x, conv):
+        from . import ops
+        return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and ops.pw8_conv_covers(x, self.cin, self.cout)
+                and x.is_contiguous(memory_format=torch.channels_last) and conv.weight.dtype == torch.bfloat16
+                and self.wt2d.dtype == torch.bfloat16 and self.wt2d.device == x.device and self.scale.device == x.device)
+
+    def _pw8(self, x, conv, res, relu6):
+        from . import ops
+        w2d = conv.weight.reshape(self.cout, self.cin)
+        if not w2d.is_contiguous():
+            w2d = w2d.contiguous()
+        return ops.pw8_conv(x, w2d, self.wt2d, self.scale, self.shift, res, relu6)
+
+
+class _OwnPointwise(_Pw8Tables, nn.Sequential):
+    """A `_ConvBNReLU6` whose convolution is 1x1 / stride 1 / groups 1, run as ONE kernel pass (`ops.pw8_conv`: GEMM,
+    eval-BatchNorm and ReLU6 on the accumulators) where the kernel covers the input.  The original conv / bn / ReLU6 stay
+    as submodules '0' / '1' / '2' (same state_dict keys; they serve every other input: CPU, fp32, not channels_last)."""
+
+    def __init__(self, block: _ConvBNReLU6):
+        nn.Sequential.__init__(self, *block.children())
+        if not _is_pointwise_block(block):
+            raise ValueError("not a 1x1 conv + BatchNorm + ReLU6 block")
+        self._init_tables(self[0], self[1])
+
+    def forward(self, x):
+        if self._covers(x, self[0]):
+            return self._pw8(x, self[0], None, True)
+        return nn.Sequential.forward(self, x)
+
+
+class _OwnInvertedResidual(_Pw8Tables):
+    """An `_InvertedResidual` whose projection (1x1 convolution, BatchNorm, and the residual add of the ten residual
+    blocks) is ONE `ops.pw8_conv` call with `res=x`.  The layers stay in `conv` under their original names (same
+    state_dict keys); the layers in front of the projection run as they are (rewritten or not), and the projection's own
+    conv / bn serve every input the kernel does not cover."""
+
+    def __init__(self, block: _InvertedResidual):
+        super().__init__()
+        if not _is_projection_block(block):
+            raise ValueError("not an inverted residual block with a 1x1 projection + BatchNorm")
+        self.use_res, self.conv = block.use_res, block.conv
+        self._init_tables(self.conv[-2], self.conv[-1])
+
+    def forward(self, x):
+        layers = list(self.conv)
+        h = x
+        for layer in layers[:-2]:
+            h = layer(h)
+        if self._covers(h, layers[-2]) and (not self.use_res or (x.dtype == h.dtype and x.shape == (h.shape[0], self.cout)
+                                                                  + tuple(h.shape[2:]))):
+            return self._pw8(h, layers[-2], x if self.use_res else None, False)
+        h = layers[-1](layers[-2](h))
+        return x + h if self.use_res else h
+
+
+def _is_projection_block(block) -> bool:
+    return (isinstance(block, _InvertedResidual) and isinstance(block.conv, nn.Sequential) and len(block.conv) >= 3
+            and _is_pointwise(block.conv[-2], block.conv[-1]))
+
+
+def use_own_pointwise_(net: nn.Module) -> int:
+    """Replace every 1x1 `_ConvBNReLU6` of the network by an `_OwnPointwise` and every `_InvertedResidual` by an
+    `_OwnInvertedResidual`; returns how many 1x1 layers were rewritten (MobileNetV2: 16 expansions, 17 projections and
+    the 320 -> 1280 layer)."""
+    n = 0
+    for parent in list(net.modules()):
+        for name, child in list(parent._modules.items()):
+            if _is_pointwise_block(child):
+                parent._modules[name] = _OwnPointwise(child)
+                n += 1
+            elif _is_projection_block(child):
+                parent._modules[name] = _OwnInvertedResidual(child)
+                n += 1
+    return n
+
+
 class _ConvAffine(_Fp32Tables):
     """conv (weights untouched) followed by the fused eval-BatchNorm [+ residual] [+ ReLU] epilogue kernel."""
 
@@ -999,7 +1108,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      device=None, dtype: torch.dtype = torch.float32, channels_last: bool = False,
                      fold_bn: bool = False, pad_input_channels: int = 0, fuse_bn_act: bool = False,
                      fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False,
-                     own_depthwise: bool = False) -> nn.Module:
+                     own_depthwise: bool = False, own_pointwise: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
@@ -1008,7 +1117,9 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     "inference" = only inside engine.precise_head (the DDrague inference solver), see FusedResNet; own_strided_conv (with
     fuse_bn_act) runs the stride-2 3x3 convolutions in the hand-written kernel instead of the library (off by default);
     own_depthwise (MobileNetV2, bf16, channels_last) runs the 17 depthwise 3x3 layers with their BatchNorm and ReLU6 in
-    the hand-written kernel (`_OwnDepthwise`; off by default)."""
+    the hand-written kernel (`_OwnDepthwise`; off by default); own_pointwise (same conditions, independent of
+    own_depthwise) runs the 34 1x1 layers with their BatchNorm, ReLU6 and residual add in the narrow-channel GEMM kernel
+    (`_OwnPointwise` / `_OwnInvertedResidual`; off by default)."""
     if head_fp32 and not fuse_bn_act:
         raise ValueError("head_fp32 is a switch of the FusedResNet path (fuse_bn_act=True)")
     if own_strided_conv and not fuse_bn_act:
@@ -1020,6 +1131,12 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         raise ValueError("own_depthwise needs a bfloat16 network (the depthwise kernels read and write bf16 activations)")
     if own_depthwise and not channels_last:
         raise ValueError("own_depthwise needs channels_last=True (the depthwise kernels work on channels_last storage)")
+    if own_pointwise and key != 'mobilenet_v2':
+        raise ValueError("own_pointwise is a switch of MobileNetV2 (the 1x1 layers of no other network are rewritten)")
+    if own_pointwise and dtype != torch.bfloat16:
+        raise ValueError("own_pointwise needs a bfloat16 network (the pointwise kernels read and write bf16 activations)")
+    if own_pointwise and not channels_last:
+        raise ValueError("own_pointwise needs channels_last=True (the pointwise kernels work on channels_last storage)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1031,6 +1148,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     stem_fused = False
     if own_depthwise:                    # after the weights are loaded: the tables are folded from them
         use_own_depthwise_(net)
+    if own_pointwise:
+        use_own_pointwise_(net)
     if fuse_bn_act and isinstance(net, ResNet):
         stem_fused = bool(fuse_stem)
         if stem_fused and dtype != torch.bfloat16:

@@ -51,7 +51,7 @@ extern "C" {
  * stores — ADIL_U8 as a source of adil_gather_images, adil_images_to_u8, adil_synth_store.  adil_pw_join_fwd /
  * adil_pw_join_bwd, and after them adil_conv3x3_s2_fwd / adil_conv3x3_s2_bwd, were added under 8: new symbols only, no
  * existing signature changed, and a library without them fails to load by name.  adil_dw3x3_fwd / adil_dw3x3_bwd joined them the
- * same way. */
+ * same way, and adil_pw8_fwd / adil_pw8_bwd after them. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -374,6 +374,30 @@ int adil_dw3x3_fwd(const void* x, const float* w, const float* bias, void* y, in
                    int relu6, void* stream);
 int adil_dw3x3_bwd(const void* g, const void* y, const float* w, void* gx, int B, int H, int W, int C, int stride,
                    int relu6, void* stream);
+
+/* Pointwise (1x1, stride 1) convolution of the frozen network for channel counts that are multiples of 8 (the 34 such
+ * layers of MobileNetV2: 16 / 24 / 32 / 96 / 144 / 160 / 192 / 320 / 384 / 576 / 960 / 1280 channels) on channels_last
+ * storage, i.e. a row-major GEMM over M = B H W pixels, with the layer's eval-BatchNorm, the residual add and the ReLU6
+ * clamp applied on the accumulators: bf16 in / out, bf16 MFMA with fp32 accumulation, fp32 epilogue, ONE rounding to bf16
+ * (nearest even).
+ *   scale, shift [N] fp32 : scale = gamma / sqrt(var + eps), shift = beta - mean * scale (derived in fp64)
+ *   adil_pw8_fwd : y[M][N] = act( (x[M][K] . w[N][K]^T) * scale[n] + shift[n] (+ res[M][N]) ),
+ *                  act 0 = the identity (the linear bottleneck), act 1 = min(max(., 0), 6) before the rounding; every
+ *                  pre-activation <= 0 is written as +0, never -0.0.  res may be NULL and is allowed only with act 0.
+ *   adil_pw8_bwd : gz = bf16(g * scale[n]) (one fp32 product, one rounding), with act 1 masked by [0 < y < 6];
+ *                  gx[M][K] = gz . wt^T with wt[K][N] the TRANSPOSED weight (the reduction index is contiguous, as in
+ *                  adil_pw_conv_bwd).  The mask is taken from the stored bf16 y by comparing VALUES (-0.0 in y is a zero:
+ *                  no precondition); act 0: y may be NULL.  There is no gradient output for res: it is g itself.
+ *                  Every element of gx is written.  Input gradient only: the network is frozen.
+ * K % 8 == 0, N % 8 == 0, 8 <= K, N <= 2048 (no multiple of 16, 32 or 64 is needed), any M >= 1, 16-byte aligned
+ * pointers; anything else, a NULL mandatory pointer, res with act 1 or act outside {0, 1}: ADIL_EINVAL before any launch,
+ * outputs untouched.  No load or store leaves the M x K, N x K, M x N extents: the K tail and the N tail are clipped and
+ * zero-filled.  Element offsets are 64-bit (M N may pass 2^31).  One launch on `stream`, no synchronisation, no
+ * allocation.  No atomics: bitwise reproducible. */
+int adil_pw8_fwd(const void* x, const void* w, const float* scale, const float* shift, const void* res, void* y, int M,
+                 int K, int N, int act, void* stream);
+int adil_pw8_bwd(const void* g, const void* y, const float* scale, const void* wt, void* gx, int M, int K, int N, int act,
+                 void* stream);
 
 #ifdef __cplusplus
 }
