@@ -64,7 +64,9 @@ __device__ __forceinline__ void atomic_max_nonneg(float* addr, float v) {
 }
 
 // --------------------------------------------------------------------------- //
-// AdamW (torch.optim.AdamW single-tensor semantics) on one element
+// AdamW on one element: the operation sequence of torch.optim.AdamW's single-tensor path, with the weights 1 - b formed
+// in fp32 from the fp32 betas (1.0f - 0.999f = 0.00099998713, torch: 0.001 formed in double), so close to torch but not
+// bitwise torch (include/adil_hip.h, adil_adamw_clamp; tests/update_reference.py restates this function bit for bit)
 // --------------------------------------------------------------------------- //
 struct AdamWHyper {
     float decay;      // 1 - lr*wd
