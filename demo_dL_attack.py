@@ -72,6 +72,11 @@ def build_parser():
                    help='-m mobilenet --dtype bf16: 1 = the 34 1x1 layers (with their BatchNorm, ReLU6 and residual add) run '
                         'in the narrow-channel GEMM kernel on channels_last storage; 0 (default) = the library.  Independent '
                         'of --own-depthwise.  Ignored otherwise')
+    p.add_argument('--own-first-conv', type=int, default=0, choices=[0, 1],
+                   help='-m mobilenet --dtype bf16: 1 = the normalisation and the 3 -> 32 first convolution (with its BatchNorm '
+                        'and ReLU6) run in the first-convolution kernels on the attack\'s own tensors; 0 (default) = the '
+                        'library.  Independent of the other two; with all three no library convolution is left.  Ignored '
+                        'otherwise')
     return p
 
 
@@ -133,8 +138,10 @@ def main(args):
         weights = _fitted_weights(model_name, args.seed, train_dataset, n_classes, device)
     mobile_bf16 = dtype == torch.bfloat16 and zoo.canonical_name(model_name) == 'mobilenet_v2'
     own_dw, own_pw = bool(args.own_depthwise) and mobile_bf16, bool(args.own_pointwise) and mobile_bf16
+    own_fc = bool(args.own_first_conv) and mobile_bf16
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
-                                 channels_last=fast or own_dw or own_pw, own_depthwise=own_dw, own_pointwise=own_pw, fuse_bn_act=fast,
+                                 channels_last=fast or own_dw or own_pw or own_fc, own_depthwise=own_dw, own_pointwise=own_pw,
+                                 own_first_conv=own_fc, fuse_bn_act=fast,
                                  fuse_stem=fast,
                                  head_fp32="inference" if fast else False,      # fp32 logits inside the DDrague inference loop
                                  own_strided_conv=fast and bool(args.own_strided_conv))

@@ -1231,6 +1231,83 @@ def resnet_stem(x: Tensor, w_fwd: Tensor, w_bwd: Tensor, scale: Tensor, shift: T
 
 
 # --------------------------------------------------------------------------- #
+FIRST3X3_MAX_BATCH = 65535   # the image index is a grid dimension of adil_first3x3_fwd / _bwd (include/adil_hip.h)
+
+
+def pack_first3x3_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
+    """(32,3,3,3) conv weight -> the two bf16 layouts of adil_first3x3_fwd / _bwd (include/adil_hip.h), both 2-D:
+    w_fwd [32][3*4*4] (w[n][c][kh][kw] at [n][kh][kw][c], zero for kw = 3 / c = 3) and w_bwd [3][9*32]
+    (w[n][c][kh][kw] at [c][kh*3+kw][n]: channels swapped, taps NOT flipped)."""
+    if tuple(weight.shape) != (32, 3, 3, 3):
+        raise ValueError(f"first-convolution kernels are written for a (32,3,3,3) convolution, got {tuple(weight.shape)}")
+    w = weight.detach().float()
+    wf = torch.zeros(32, 3, 4, 4, dtype=torch.float32, device=w.device)
+    wf[:, :, :3, :3] = w.permute(0, 2, 3, 1)                       # [n][kh][kw][c]
+    wb = w.permute(1, 2, 3, 0).reshape(3, 9 * 32)                   # [c][kh*3+kw][n]
+    # 2-D on purpose: nn.Module.to(memory_format=channels_last) re-strides every 4-D buffer
+    return wf.to(torch.bfloat16).reshape(32, 48).contiguous(), wb.to(torch.bfloat16).contiguous()
+
+
+def first_conv3x3_covers(x: Tensor) -> bool:
+    """What adil_first3x3_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype in _DTYPE_CODE and x.shape[1] == 3 and x.shape[2] > 0
+            and x.shape[3] > 0 and x.shape[0] <= FIRST3X3_MAX_BATCH)
+
+
+class FirstConv3x3Function(torch.autograd.Function):
+    """Normalize -> conv3x3/2 (3 -> 32) -> BatchNorm(eval) (-> ReLU6) of a frozen MobileNetV2 as one HIP kernel
+    (adil_first3x3_fwd) and its input gradient, ReLU6 mask from the saved output, as another (adil_first3x3_bwd).
+    x: (B,3,H,W) fp32/bf16 contiguous NCHW; returns (B,32,OH,OW) bf16 in channels_last storage.  The gradient comes
+    back in x's dtype and layout.  No weight gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, w_fwd, w_bwd, scale, shift, mean, inv_std, relu6):
+        lib = _lib.load()
+        b, _, h, w = x.shape
+        oh, ow = (h - 1) // 2 + 1, (w - 1) // 2 + 1
+        y = torch.empty((b, oh, ow, 32), dtype=torch.bfloat16, device=x.device)
+        if b > 0:
+            _lib.check(lib.adil_first3x3_fwd(_ptr(x), stream_dtype_code(x.dtype), _ptr(w_fwd), *mean, *inv_std, _ptr(scale),
+                                             _ptr(shift), _ptr(y), b, h, w, int(relu6), _stream()), "adil_first3x3_fwd")
+        ctx.save_for_backward(w_bwd, scale, y if relu6 else None)
+        ctx.meta = (h, w, x.dtype, inv_std, int(relu6))
+        return y.permute(0, 3, 1, 2)                                 # logical NCHW, channels_last storage
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        w_bwd, scale, y = ctx.saved_tensors
+        h, w, xdtype, inv_std, relu6 = ctx.meta
+        g2 = g.permute(0, 2, 3, 1)
+        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
+            g2 = g2.to(torch.bfloat16).contiguous()
+        b = g2.shape[0]
+        gx = torch.empty((b, 3, h, w), dtype=xdtype, device=g2.device)
+        if b > 0:
+            _lib.check(lib.adil_first3x3_bwd(_ptr(g2), _ptr(y), _ptr(scale), _ptr(w_bwd), *inv_std, _ptr(gx),
+                                             stream_dtype_code(xdtype), b, h, w, relu6, _stream()), "adil_first3x3_bwd")
+        return (gx,) + (None,) * 7
+
+
+def first_conv3x3(x: Tensor, w_fwd: Tensor, w_bwd: Tensor, scale: Tensor, shift: Tensor, mean, inv_std,
+                  relu6: bool = True) -> Tensor:
+    """x (B,3,H,W) fp32 / bf16, contiguous NCHW -> relu6(bn(conv3x3/2((x - mean) / std))) as (B,32,OH,OW) bf16 in
+    channels_last memory format, no copies.  mean / inv_std: three floats each."""
+    if not first_conv3x3_covers(x):
+        raise ValueError(f"adil_first3x3 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous (NCHW)")
+    for name, t, shape, dt in (("w_fwd", w_fwd, (32, 48), torch.bfloat16), ("w_bwd", w_bwd, (3, 288), torch.bfloat16),
+                               ("scale", scale, (32,), torch.float32), ("shift", shift, (32,), torch.float32)):
+        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
+            raise ValueError(f"{name} must be a contiguous {shape} {dt} tensor on {x.device}")
+    mean, inv_std = tuple(float(m) for m in mean), tuple(float(s) for s in inv_std)
+    if len(mean) != 3 or len(inv_std) != 3:
+        raise ValueError("mean and inv_std must hold three values each")
+    return FirstConv3x3Function.apply(x, w_fwd, w_bwd, scale, shift, mean, inv_std, bool(relu6))
+
+
+# --------------------------------------------------------------------------- #
 class DictSynthFunction(torch.autograd.Function):
     """x + D v[index] as a differentiable op (the tensordot of adil.py:25 and its autograd backward).
     grad wrt v is dense (N,K) with zero rows outside `index`, exactly what autograd produces."""

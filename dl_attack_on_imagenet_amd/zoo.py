@@ -793,6 +793,69 @@ def use_own_pointwise_(net: nn.Module) -> int:
     return n
 
 
+def _is_first_conv_block(block) -> bool:
+    if not isinstance(block, _ConvBNReLU6) or len(block) != 3:
+        return False
+    conv, bn = block[0], block[1]
+    return (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and conv.in_channels == 3
+            and conv.out_channels == 32 and conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros')
+
+
+class _OwnFirstConv(nn.Sequential):
+    """`features[0]` of MobileNetV2 (a `_ConvBNReLU6` with conv 3 -> 32, 3x3, stride 2, pad 1, groups 1, no bias) together
+    with the `Normalize` in front of the network, run as ONE kernel pass (`ops.first_conv3x3`) on the attack's own
+    (B,3,H,W) fp32 / bf16 tensor where the kernel covers the input; its backward produces dLoss/dx in the layout
+    `adil_grad` reads.  The original conv / bn / ReLU6 stay as submodules '0' / '1' / '2' (same state_dict keys); on every
+    other input (CPU, fp32 network, wrong channel count) the module normalises in torch exactly as `Normalize` does and
+    runs them, so the rewritten network is the same function everywhere.  Non-persistent buffers (no state_dict
+    entries): `scale` / `shift` from `_bn_affine`, kept fp32 under `.to(bfloat16)` and following device moves; the packed
+    weights `w_fwd` / `w_bwd` and the `Normalize` tables `norm_mean` / `norm_std`, cast with the network.  The kernel takes
+    `mean` and `inv_std` as plain floats."""
+    _TABLES = ('scale', 'shift')
+
+    def __init__(self, block: _ConvBNReLU6, mean, std):
+        super().__init__(*block.children())
+        if not _is_first_conv_block(block):
+            raise ValueError("not a 3 -> 32, 3x3, stride 2, pad 1 conv + BatchNorm + ReLU6 block")
+        from . import ops
+        conv, bn = self[0], self[1]
+        w_fwd, w_bwd = ops.pack_first3x3_weights(conv.weight)
+        scale, shift = _bn_affine(bn)
+        self.mean = [float(m) for m in mean]
+        self.inv_std = [1.0 / float(s) for s in std]
+        for name, t in (('scale', scale), ('shift', shift), ('w_fwd', w_fwd), ('w_bwd', w_bwd),
+                        ('norm_mean', torch.tensor(self.mean, dtype=torch.float32, device=conv.weight.device)),
+                        ('norm_std', torch.tensor([float(v) for v in std], dtype=torch.float32, device=conv.weight.device))):
+            self.register_buffer(name, t, persistent=False)
+
+    def _apply(self, fn, recurse=True):
+        keep = {n: getattr(self, n) for n in self._TABLES}
+        super()._apply(fn, recurse)
+        for n, t in keep.items():
+            setattr(self, n, t.to(device=fn(t).device))
+        return self
+
+    def forward(self, x):
+        from . import ops
+        if (ops.first_conv3x3_covers(x) and self[0].weight.dtype == torch.bfloat16 and self.w_fwd.dtype == torch.bfloat16
+                and self.w_fwd.device == x.device and self.scale.device == x.device):
+            return ops.first_conv3x3(x.contiguous(), self.w_fwd, self.w_bwd, self.scale, self.shift, self.mean,
+                                     self.inv_std, True)
+        mean = self.norm_mean.reshape(1, -1, 1, 1).to(x.dtype)      # `Normalize.forward`, operation for operation
+        std = self.norm_std.reshape(1, -1, 1, 1).to(x.dtype)
+        return super().forward((x - mean) / std)
+
+
+def use_own_first_conv_(net: nn.Module, mean, std) -> int:
+    """Replace `features[0]` of a MobileNetV2 by an `_OwnFirstConv`, which also takes over the normalisation: the caller
+    must no longer put a `Normalize` in front of the network.  Returns how many layers were rewritten (1)."""
+    if not isinstance(net, MobileNetV2) or not _is_first_conv_block(net.features[0]):
+        raise ValueError("own_first_conv rewrites features[0] of MobileNetV2 (conv 3 -> 32, 3x3, stride 2, pad 1)")
+    net.features[0] = _OwnFirstConv(net.features[0], mean, std)
+    return 1
+
+
 class _ConvAffine(_Fp32Tables):
     """conv (weights untouched) followed by the fused eval-BatchNorm [+ residual] [+ ReLU] epilogue kernel."""
 
@@ -1108,7 +1171,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      device=None, dtype: torch.dtype = torch.float32, channels_last: bool = False,
                      fold_bn: bool = False, pad_input_channels: int = 0, fuse_bn_act: bool = False,
                      fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False,
-                     own_depthwise: bool = False, own_pointwise: bool = False) -> nn.Module:
+                     own_depthwise: bool = False, own_pointwise: bool = False,
+                     own_first_conv: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
@@ -1119,7 +1183,9 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     own_depthwise (MobileNetV2, bf16, channels_last) runs the 17 depthwise 3x3 layers with their BatchNorm and ReLU6 in
     the hand-written kernel (`_OwnDepthwise`; off by default); own_pointwise (same conditions, independent of
     own_depthwise) runs the 34 1x1 layers with their BatchNorm, ReLU6 and residual add in the narrow-channel GEMM kernel
-    (`_OwnPointwise` / `_OwnInvertedResidual`; off by default)."""
+    (`_OwnPointwise` / `_OwnInvertedResidual`; off by default); own_first_conv (same conditions, independent of the other
+    two) moves the normalisation and the 3 -> 32 first convolution with its BatchNorm and ReLU6 into the first-convolution
+    kernels (`_OwnFirstConv`; the Sequential then holds the network alone, as with fuse_stem; off by default)."""
     if head_fp32 and not fuse_bn_act:
         raise ValueError("head_fp32 is a switch of the FusedResNet path (fuse_bn_act=True)")
     if own_strided_conv and not fuse_bn_act:
@@ -1137,6 +1203,12 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         raise ValueError("own_pointwise needs a bfloat16 network (the pointwise kernels read and write bf16 activations)")
     if own_pointwise and not channels_last:
         raise ValueError("own_pointwise needs channels_last=True (the pointwise kernels work on channels_last storage)")
+    if own_first_conv and key != 'mobilenet_v2':
+        raise ValueError("own_first_conv is a switch of MobileNetV2 (the first convolution of no other network is rewritten)")
+    if own_first_conv and dtype != torch.bfloat16:
+        raise ValueError("own_first_conv needs a bfloat16 network (the first-convolution kernels write bf16 activations)")
+    if own_first_conv and not channels_last:
+        raise ValueError("own_first_conv needs channels_last=True (the first-convolution kernels write channels_last storage)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1150,6 +1222,9 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         use_own_depthwise_(net)
     if own_pointwise:
         use_own_pointwise_(net)
+    if own_first_conv:                   # the module normalises: the Sequential holds the network alone
+        use_own_first_conv_(net, mean, std)
+        stem_fused = True
     if fuse_bn_act and isinstance(net, ResNet):
         stem_fused = bool(fuse_stem)
         if stem_fused and dtype != torch.bfloat16:

@@ -51,7 +51,7 @@ extern "C" {
  * stores — ADIL_U8 as a source of adil_gather_images, adil_images_to_u8, adil_synth_store.  adil_pw_join_fwd /
  * adil_pw_join_bwd, and after them adil_conv3x3_s2_fwd / adil_conv3x3_s2_bwd, were added under 8: new symbols only, no
  * existing signature changed, and a library without them fails to load by name.  adil_dw3x3_fwd / adil_dw3x3_bwd joined them the
- * same way, and adil_pw8_fwd / adil_pw8_bwd after them. */
+ * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those: both additive under 8. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -413,6 +413,36 @@ int adil_pw8_fwd(const void* x, const void* w, const float* scale, const float* 
                  int K, int N, int act, void* stream);
 int adil_pw8_bwd(const void* g, const void* y, const float* scale, const void* wt, void* gx, int M, int K, int N, int act,
                  void* stream);
+
+/* First convolution of the frozen MobileNetV2 (features[0]: 3 -> 32, 3x3, stride 2, pad 1, no bias) with the Normalize in
+ * front of it and its eval-BatchNorm + ReLU6 behind it, forward and input gradient, on the attack's own layouts: x_adv /
+ * dLoss/dx_adv are [B][3][H][W] NCHW in the stream dtype (ADIL_F32 / ADIL_BF16, the codes of adil_stem_conv_fwd), the
+ * activation side is [B][OH][OW][32] channels_last bf16.  H, W are the INPUT grid in both calls, any H, W >= 1 (odd sizes
+ * included); OH x OW = (H-1)/2 + 1 x (W-1)/2 + 1.  bf16 MFMA with fp32 accumulation.  Weights are pre-packed bf16:
+ *     w_fwd [32][3][4][4] = w[n][c][kh][kw] at [n][kh][kw][c], zero for kw = 3 / c = 3 (K = 27 padded to 3 x 16)
+ *     w_bwd [3][9][32]    = w[n][c][kh][kw] at [c][kh*3+kw][n] (taps NOT flipped, channels swapped, as adil_conv3x3_s2_bwd)
+ *   scale, shift [32] fp32 : scale = gamma / sqrt(var + eps), shift = beta - mean * scale (derived in fp64)
+ *   adil_first3x3_fwd : x' = bf16( f32( f32(x - mean[c]) * inv_std[c] ) ): the subtraction and the product each rounded to
+ *                       fp32, then nearest even to bf16; padding taps are zeros of x', not of x;
+ *                       acc = sum x'[b][c][2oh-1+kh][2ow-1+kw] * w[n][c][kh][kw] in fp32 (any order);
+ *                       y = bf16( act( acc * scale[n] + shift[n] ) ), act = min(max(., 0), 6) if relu6 else the identity;
+ *                       every pre-activation <= 0 (relu6) and every zero (relu6 == 0) is written as +0, never -0.0.
+ *   adil_first3x3_bwd : gz = bf16(g * scale[n]) (one fp32 product, one rounding), with relu6 masked by [0 < y < 6] taken
+ *                       from the stored bf16 y by comparing VALUES (-0.0 in y is a zero); relu6 == 0: y may be NULL;
+ *                       gx[b][c][h][w] = round( inv_std[c] * sum gz[b][(h+1-kh)/2][(w+1-kw)/2][n] * w[n][c][kh][kw] ) over the
+ *                       taps whose quotients are integers and in range (1 / 2 / 2 / 4 taps by the parity of (h, w); g is
+ *                       never zero-upsampled): fp32 sum in any order, ONE fp32 multiply by inv_std, one rounding when gx is
+ *                       bf16.  Every element of gx is written.  Input gradient only: the network is frozen.
+ * 16-byte aligned y, g, w_fwd, w_bwd; x and gx aligned to their element size.  A NULL mandatory pointer, a non-positive
+ * size, B > 65535 (the image index is a grid dimension), a dtype code outside the two, relu6 outside {0, 1} or a misaligned
+ * pointer: ADIL_EINVAL before any launch, outputs untouched.  No load leaves the extents of x, g or y: border taps are
+ * predicated, never clamped reads.  Element offsets are 64-bit (B OH OW 32 passes 2^31 at B ~ 5350 for 224 x 224).  One
+ * launch on `stream`, no synchronisation, no allocation.  No atomics: bitwise reproducible. */
+int adil_first3x3_fwd(const void* x, int x_dtype, const void* w_fwd, float mean0, float mean1, float mean2, float inv_std0,
+                      float inv_std1, float inv_std2, const float* scale, const float* shift, void* y, int B, int H, int W,
+                      int relu6, void* stream);
+int adil_first3x3_bwd(const void* g, const void* y, const float* scale, const void* w_bwd, float inv_std0, float inv_std1,
+                      float inv_std2, void* gx, int gx_dtype, int B, int H, int W, int relu6, void* stream);
 
 #ifdef __cplusplus
 }
