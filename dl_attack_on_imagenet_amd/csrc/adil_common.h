@@ -133,6 +133,10 @@ __device__ __forceinline__ float slab_sum(const float* __restrict__ p, int nslab
 
 static inline int round_up(int x, int m) { return (x + m - 1) / m * m; }
 
+// Host-side check of a pointer against the widest access a kernel makes through it; `bytes` is a power of two.  A null
+// pointer passes (optional arguments are tested for presence where they are required).
+static inline bool aligned(const void* p, uintptr_t bytes) { return (reinterpret_cast<uintptr_t>(p) & (bytes - 1)) == 0; }
+
 // Compute units of the current device (grid sizing, per-workgroup scratch), asked once per device.  256 (MI355X) when
 // no device can be queried — the workspace-size entry points are also called on boxes without a GPU (build check).
 static inline int adil_num_cu() {

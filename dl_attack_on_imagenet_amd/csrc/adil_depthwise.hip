@@ -216,8 +216,6 @@ __global__ __launch_bounds__(DW_THREADS) void dw3x3_bwd_kernel(const bf16_t* __r
     }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 inline bool dw_args_ok(int B, int H, int W, int C, int stride) {
     return B > 0 && H > 0 && W > 0 && C > 0 && (C % 8) == 0 && (stride == 1 || stride == 2);
 }
@@ -232,7 +230,7 @@ inline unsigned dw_grid(size_t total) {
 extern "C" int adil_dw3x3_fwd(const void* x, const float* w, const float* bias, void* y, int B, int H, int W, int C,
                               int stride, int relu6, void* stream) {
     if (x == nullptr || w == nullptr || y == nullptr || !dw_args_ok(B, H, W, C, stride)) return ADIL_EINVAL;
-    if (!aligned16(x) || !aligned16(w) || !aligned16(y) || !aligned16(bias)) return ADIL_EINVAL;
+    if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y, 16) || !aligned(bias, 16)) return ADIL_EINVAL;
     ADIL_ENTER();
     const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
     const size_t total = (size_t)B * (size_t)OH * (size_t)((OW + DW_TW - 1) / DW_TW) * (size_t)(C / 8);
@@ -255,7 +253,7 @@ extern "C" int adil_dw3x3_bwd(const void* g, const void* y, const float* w, void
                               int stride, int relu6, void* stream) {
     if (g == nullptr || w == nullptr || gx == nullptr || (relu6 && y == nullptr) || !dw_args_ok(B, H, W, C, stride))
         return ADIL_EINVAL;
-    if (!aligned16(g) || !aligned16(w) || !aligned16(gx) || (relu6 && !aligned16(y))) return ADIL_EINVAL;
+    if (!aligned(g, 16) || !aligned(w, 16) || !aligned(gx, 16) || (relu6 && !aligned(y, 16))) return ADIL_EINVAL;
     ADIL_ENTER();
     const int OH = (H - 1) / stride + 1, OW = (W - 1) / stride + 1;
     const size_t total = (size_t)B * (size_t)H * (size_t)((W + DW_TW - 1) / DW_TW) * (size_t)(C / 8);

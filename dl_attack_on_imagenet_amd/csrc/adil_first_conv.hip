@@ -247,8 +247,6 @@ __global__ __launch_bounds__(256) void first3x3_bwd_kernel(const bf16_t* __restr
     }
 }
 
-inline bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
-
 inline bool first_args_ok(int B, int H, int W, int dtype, int relu6) {
     // gridDim.z carries the image index
     return B > 0 && B <= 65535 && H > 0 && W > 0 && (dtype == ADIL_F32 || dtype == ADIL_BF16) && (relu6 == 0 || relu6 == 1);
@@ -261,8 +259,8 @@ extern "C" int adil_first3x3_fwd(const void* x, int x_dtype, const void* w_fwd, 
                                  float inv_std0, float inv_std1, float inv_std2, const float* scale, const float* shift,
                                  void* y, int B, int H, int W, int relu6, void* stream) {
     if (!x || !w_fwd || !scale || !shift || !y || !first_args_ok(B, H, W, x_dtype, relu6)) return ADIL_EINVAL;
-    if (!aligned_to(x, x_dtype == ADIL_F32 ? 4 : 2) || !aligned_to(w_fwd, 16) || !aligned_to(y, 16) || !aligned_to(scale, 4) ||
-        !aligned_to(shift, 4))
+    if (!aligned(x, x_dtype == ADIL_F32 ? 4 : 2) || !aligned(w_fwd, 16) || !aligned(y, 16) || !aligned(scale, 4) ||
+        !aligned(shift, 4))
         return ADIL_EINVAL;
     ADIL_ENTER();
     const FirstNorm nm = {{mean0, mean1, mean2}, {inv_std0, inv_std1, inv_std2}};
@@ -287,8 +285,8 @@ extern "C" int adil_first3x3_bwd(const void* g, const void* y, const float* scal
                                  float inv_std1, float inv_std2, void* gx, int gx_dtype, int B, int H, int W, int relu6,
                                  void* stream) {
     if (!g || !scale || !w_bwd || !gx || !first_args_ok(B, H, W, gx_dtype, relu6) || (relu6 && !y)) return ADIL_EINVAL;
-    if (!aligned_to(g, 16) || !aligned_to(w_bwd, 16) || (relu6 && !aligned_to(y, 16)) || !aligned_to(scale, 4) ||
-        !aligned_to(gx, gx_dtype == ADIL_F32 ? 4 : 2))
+    if (!aligned(g, 16) || !aligned(w_bwd, 16) || (relu6 && !aligned(y, 16)) || !aligned(scale, 4) ||
+        !aligned(gx, gx_dtype == ADIL_F32 ? 4 : 2))
         return ADIL_EINVAL;
     ADIL_ENTER();
     const FirstNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};

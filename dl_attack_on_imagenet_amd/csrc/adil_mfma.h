@@ -1,4 +1,5 @@
-// adil_mfma.h — small device helpers shared by the frozen-classifier kernels (adil_stem.hip, adil_convs.hip).
+// adil_mfma.h — small device helpers shared by the frozen-classifier kernels (adil_stem.hip, adil_convs.hip,
+// adil_pointwise8.hip, adil_first_conv.hip).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

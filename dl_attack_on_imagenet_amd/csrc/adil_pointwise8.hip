@@ -210,8 +210,6 @@ __global__ __launch_bounds__(256) void pw8_kernel(const bf16_t* __restrict__ a, 
     }
 }
 
-inline bool p8_aligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
-
 inline bool p8_dims_ok(int M, int K, int N, int act) {
     return M >= 1 && K >= 8 && N >= 8 && K <= P8_MAXC && N <= P8_MAXC && (K % 8) == 0 && (N % 8) == 0 && (act == 0 || act == 1);
 }
@@ -247,7 +245,7 @@ extern "C" int adil_pw8_fwd(const void* x, const void* w, const float* scale, co
     if (x == nullptr || w == nullptr || scale == nullptr || shift == nullptr || y == nullptr || !p8_dims_ok(M, K, N, act))
         return ADIL_EINVAL;
     if (res != nullptr && act != 0) return ADIL_EINVAL;
-    if (!p8_aligned(x) || !p8_aligned(w) || !p8_aligned(scale) || !p8_aligned(shift) || !p8_aligned(res) || !p8_aligned(y))
+    if (!aligned(x, 16) || !aligned(w, 16) || !aligned(scale, 16) || !aligned(shift, 16) || !aligned(res, 16) || !aligned(y, 16))
         return ADIL_EINVAL;
     ADIL_ENTER();
     hipStream_t s = (hipStream_t)stream;
@@ -264,7 +262,7 @@ extern "C" int adil_pw8_bwd(const void* g, const void* y, const float* scale, co
                             int act, void* stream) {
     if (g == nullptr || scale == nullptr || wt == nullptr || gx == nullptr || !p8_dims_ok(M, K, N, act)) return ADIL_EINVAL;
     if (act != 0 && y == nullptr) return ADIL_EINVAL;
-    if (!p8_aligned(g) || !p8_aligned(scale) || !p8_aligned(wt) || !p8_aligned(gx) || (act != 0 && !p8_aligned(y)))
+    if (!aligned(g, 16) || !aligned(scale, 16) || !aligned(wt, 16) || !aligned(gx, 16) || (act != 0 && !aligned(y, 16)))
         return ADIL_EINVAL;
     ADIL_ENTER();
     p8_dispatch<true, false>((const bf16_t*)g, act ? (const bf16_t*)y : nullptr, (const bf16_t*)wt, scale, nullptr, nullptr,

@@ -22,10 +22,6 @@ namespace {
 
 struct StemNorm { float mean[3]; float inv_std[3]; };
 
-template <typename T> __device__ __forceinline__ float ld_px(const T* p, size_t i);
-template <> __device__ __forceinline__ float ld_px<float>(const float* p, size_t i) { return p[i]; }
-template <> __device__ __forceinline__ float ld_px<bf16_t>(const bf16_t* p, size_t i) { return bf16_to_f32(p[i]); }
-
 // =========================================================================================================== //
 // stem_conv_fwd.  Workgroup (4 waves) = a 16 x 16 tile of conv outputs of one image, all 64 channels.
 //   K order per tap row kh: (kw 0..7, ci 0..3) = 32 values, kw = 7 and ci = 3 carrying zero weights, so that with the
@@ -81,9 +77,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
         const bool ok = (ih >= 0) && (ih < H) && (iw >= 0) && (iw < W);
         const size_t at = (size_t)(ok ? ih : 0) * W + (ok ? iw : 0);
         okm[j] = ok ? 1.0f : 0.0f;
-        raw[j][0] = ld_px<TX>(xn, at);
-        raw[j][1] = ld_px<TX>(xn + (size_t)H * W, at);
-        raw[j][2] = ld_px<TX>(xn + (size_t)2 * H * W, at);
+        raw[j][0] = Elem<TX>::load(xn, at);
+        raw[j][1] = Elem<TX>::load(xn + (size_t)H * W, at);
+        raw[j][2] = Elem<TX>::load(xn + (size_t)2 * H * W, at);
     }
 #pragma unroll
     for (int j = 0; j < NPOS; ++j) {

@@ -750,6 +750,27 @@ def affine_act(x: Tensor, scale: Tensor, shift: Tensor, res: Optional[Tensor] = 
     return AffineActFunction.apply(x, res, scale, shift, relu)
 
 
+def _nhwc(t: Tensor) -> Tensor:
+    """A logical-NCHW activation as its NHWC view, which is what the kernels index: channels_last storage is read in
+    place, anything else is copied once."""
+    t2 = t.permute(0, 2, 3, 1)
+    return t2 if t2.is_contiguous() else t2.contiguous()
+
+
+def _nhwc_grad(g: Tensor) -> Tensor:
+    """An incoming gradient as a contiguous bf16 NHWC tensor: a view when it already is one (the gradients the kernels
+    here hand to each other are), else one cast and / or one copy."""
+    g2 = g.permute(0, 2, 3, 1)
+    return g2 if (g2.is_contiguous() and g2.dtype == torch.bfloat16) else g2.to(torch.bfloat16).contiguous()
+
+
+def _check_operands(device: torch.device, *operands) -> None:
+    """Every (name, tensor, shape, dtype) must be a contiguous `shape` `dtype` tensor on `device`."""
+    for name, t, shape, dtype in operands:
+        if t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
+            raise ValueError(f"{name} must be a contiguous {shape} {dtype} tensor on {device}")
+
+
 # --------------------------------------------------------------------------- #
 class PointwiseConvFunction(torch.autograd.Function):
     """y = act(conv1x1(x') * scale + shift (+ res)) on channels_last bf16 tensors as ONE kernel (adil_pw_conv_fwd: the
@@ -778,14 +799,8 @@ class PointwiseConvFunction(torch.autograd.Function):
             else:
                 x2 = x.permute(0, 2, 3, 1).contiguous()
         else:
-            x2 = x.permute(0, 2, 3, 1)
-            if not x2.is_contiguous():
-                x2 = x2.contiguous()
-        r2 = None
-        if res is not None:
-            r2 = res.permute(0, 2, 3, 1)
-            if not r2.is_contiguous():
-                r2 = r2.contiguous()
+            x2 = _nhwc(x)
+        r2 = _nhwc(res) if res is not None else None
         y = torch.empty((b, h, w, cout), dtype=torch.bfloat16, device=x.device)
         if b > 0:                                                     # empty batches pass through like plain torch modules
             _lib.check(lib.adil_pw_conv_fwd(_ptr(x2), _ptr(w2d), _ptr(scale), _ptr(shift), _ptr(r2), _ptr(y), b * h * w, cin,
@@ -813,17 +828,12 @@ class PointwiseConvFunction(torch.autograd.Function):
             if g_sub is not None:
                 raise RuntimeError("a stride-2 gradient arrived without a full-resolution one")
             return (None,) * 11
-
-        def nhwc(t):
-            t2 = t.permute(0, 2, 3, 1)
-            return t2 if (t2.is_contiguous() and t2.dtype == torch.bfloat16) else t2.to(torch.bfloat16).contiguous()
-
-        g2 = nhwc(g)
-        gt = nhwc(g_twin) if g_twin is not None else None
+        g2 = _nhwc_grad(g)
+        gt = _nhwc_grad(g_twin) if g_twin is not None else None
         b, h, w, cout = g2.shape
         g3, sub_w, sub_hw = None, 0, 0
         if g_sub is not None:
-            g3 = nhwc(g_sub)
+            g3 = _nhwc_grad(g_sub)
             sub_w, sub_hw = g3.shape[2], g3.shape[1] * g3.shape[2]
             if (h, w) != (2 * g3.shape[1], 2 * g3.shape[2]):
                 raise RuntimeError("stride-2 gradient does not match an even full-resolution grid")
@@ -864,12 +874,7 @@ class PointwiseJoinFunction(torch.autograd.Function):
         lib = _lib.load()
         b, wd, h, w = h2raw.shape
         c = w3.shape[0]
-        h2 = h2raw.permute(0, 2, 3, 1)
-        if not h2.is_contiguous():
-            h2 = h2.contiguous()
-        r2 = x.permute(0, 2, 3, 1)
-        if not r2.is_contiguous():
-            r2 = r2.contiguous()
+        h2, r2 = _nhwc(h2raw), _nhwc(x)
         out = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=h2raw.device)
         h1 = torch.empty((b, h, w, wd), dtype=torch.bfloat16, device=h2raw.device)
         if b > 0:                                                     # empty batches pass through like plain torch modules
@@ -883,12 +888,7 @@ class PointwiseJoinFunction(torch.autograd.Function):
     def backward(ctx, g_out, g_h1):
         lib = _lib.load()
         h2, out, h1, wt3, scale2, shift2, scale3, wt1, scale1 = ctx.saved_tensors
-
-        def nhwc(t):
-            t2 = t.permute(0, 2, 3, 1)
-            return t2 if (t2.is_contiguous() and t2.dtype == torch.bfloat16) else t2.to(torch.bfloat16).contiguous()
-
-        go, gh = nhwc(g_out), nhwc(g_h1)
+        go, gh = _nhwc_grad(g_out), _nhwc_grad(g_h1)
         b, h, w, c = out.shape
         wd = h1.shape[3]
         gx = torch.empty_like(h2)
@@ -928,9 +928,7 @@ class Conv3x3Function(torch.autograd.Function):
         lib = _lib.load()
         b, c, h, w = x.shape
         n = wp_fwd.shape[0]
-        x2 = x.permute(0, 2, 3, 1)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _nhwc(x)
         y = torch.empty((b, h, w, n), dtype=torch.bfloat16, device=x.device)
         if b > 0:
             _lib.check(lib.adil_conv3x3(_ptr(x2), _ptr(wp_fwd), _ptr(y), b, h, w, c, n, _stream()), "adil_conv3x3")
@@ -943,9 +941,7 @@ class Conv3x3Function(torch.autograd.Function):
         lib = _lib.load()
         (wp_bwd,) = ctx.saved_tensors
         (c,) = ctx.meta
-        g2 = g.permute(0, 2, 3, 1)
-        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
-            g2 = g2.to(torch.bfloat16).contiguous()
+        g2 = _nhwc_grad(g)
         b, h, w, n = g2.shape
         gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
         if b > 0:
@@ -990,9 +986,7 @@ class Conv3x3S2Function(torch.autograd.Function):
         lib = _lib.load()
         b, c, h, w = x.shape
         n = wp_fwd.shape[0]
-        x2 = x.permute(0, 2, 3, 1)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _nhwc(x)
         y = torch.empty((b, h // 2, w // 2, n), dtype=torch.bfloat16, device=x.device)
         if b > 0:
             _lib.check(lib.adil_conv3x3_s2_fwd(_ptr(x2), _ptr(wp_fwd), _ptr(y), b, h, w, c, n, _stream()),
@@ -1006,9 +1000,7 @@ class Conv3x3S2Function(torch.autograd.Function):
         lib = _lib.load()
         (wp_bwd,) = ctx.saved_tensors
         c, h, w = ctx.meta
-        g2 = g.permute(0, 2, 3, 1)
-        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
-            g2 = g2.to(torch.bfloat16).contiguous()
+        g2 = _nhwc_grad(g)
         b, n = g2.shape[0], g2.shape[3]
         gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
         if b > 0:
@@ -1049,9 +1041,7 @@ class DepthwiseConv3x3Function(torch.autograd.Function):
     def forward(ctx, x, w9c, bias, stride, relu6):
         lib = _lib.load()
         b, c, h, w = x.shape
-        x2 = x.permute(0, 2, 3, 1)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
+        x2 = _nhwc(x)
         oh, ow = (h - 1) // stride + 1, (w - 1) // stride + 1
         y = torch.empty((b, oh, ow, c), dtype=torch.bfloat16, device=x.device)
         if b > 0:
@@ -1066,9 +1056,7 @@ class DepthwiseConv3x3Function(torch.autograd.Function):
         lib = _lib.load()
         w9c, y = ctx.saved_tensors
         h, w, stride, relu6 = ctx.meta
-        g2 = g.permute(0, 2, 3, 1)
-        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
-            g2 = g2.to(torch.bfloat16).contiguous()
+        g2 = _nhwc_grad(g)
         b, c = g2.shape[0], g2.shape[3]
         gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
         if b > 0:
@@ -1082,21 +1070,22 @@ def dw_conv3x3(x: Tensor, w9c: Tensor, bias: Optional[Tensor], stride: int = 1, 
     c = x.shape[1]
     if not dw_conv3x3_covers(x, c):
         raise ValueError(f"adil_dw3x3 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
-    if w9c.dtype != torch.float32 or tuple(w9c.shape) != (9, c) or not w9c.is_contiguous() or w9c.device != x.device:
-        raise ValueError(f"w9c must be a contiguous (9, {c}) float32 table on {x.device}")
-    if bias is not None and (bias.dtype != torch.float32 or tuple(bias.shape) != (c,) or not bias.is_contiguous()
-                             or bias.device != x.device):
-        raise ValueError(f"bias must be a contiguous ({c},) float32 table on {x.device}")
+    _check_operands(x.device, ("w9c", w9c, (9, c), torch.float32))
+    if bias is not None:
+        _check_operands(x.device, ("bias", bias, (c,), torch.float32))
     if stride not in (1, 2):
         raise ValueError(f"stride must be 1 or 2, got {stride}")
     return DepthwiseConv3x3Function.apply(x, w9c, bias, stride, relu6)
 
 
 # --------------------------------------------------------------------------- #
+PW8_CHANNELS = range(8, 2048 + 1, 8)    # channel counts of adil_pw8_fwd / _bwd, either side (include/adil_hip.h)
+
+
 def pw8_conv_covers(x: Tensor, cin: int, cout: int) -> bool:
     """What adil_pw8_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
-    ok = lambda c: 8 <= c <= 2048 and c % 8 == 0
-    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == cin and ok(cin) and ok(cout)
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == cin and cin in PW8_CHANNELS
+            and cout in PW8_CHANNELS
             and 1 <= x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
 
 
@@ -1110,14 +1099,8 @@ class Pointwise8Function(torch.autograd.Function):
         lib = _lib.load()
         b, k, h, w = x.shape
         n = w2d.shape[0]
-        x2 = x.permute(0, 2, 3, 1)
-        if not x2.is_contiguous():
-            x2 = x2.contiguous()
-        r2 = None
-        if res is not None:
-            r2 = res.permute(0, 2, 3, 1)
-            if not r2.is_contiguous():
-                r2 = r2.contiguous()
+        x2 = _nhwc(x)
+        r2 = _nhwc(res) if res is not None else None
         y = torch.empty((b, h, w, n), dtype=torch.bfloat16, device=x.device)
         _lib.check(lib.adil_pw8_fwd(_ptr(x2), _ptr(w2d), _ptr(scale), _ptr(shift), _ptr(r2), _ptr(y), b * h * w, k, n,
                                     int(bool(relu6)), _stream()), "adil_pw8_fwd")
@@ -1130,9 +1113,7 @@ class Pointwise8Function(torch.autograd.Function):
         lib = _lib.load()
         wt2d, scale, y = ctx.saved_tensors
         k, n, relu6, has_res = ctx.meta
-        g2 = g.permute(0, 2, 3, 1)
-        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
-            g2 = g2.to(torch.bfloat16).contiguous()
+        g2 = _nhwc_grad(g)
         b, h, w = g2.shape[0], g2.shape[1], g2.shape[2]
         gx = None
         if ctx.needs_input_grad[0]:
@@ -1153,10 +1134,8 @@ def pw8_conv(x: Tensor, w2d: Tensor, wt2d: Tensor, scale: Tensor, shift: Tensor,
     n, k = w2d.shape
     if not pw8_conv_covers(x, k, n):
         raise ValueError(f"adil_pw8 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with a {n} x {k} weight")
-    for name, t, shape, dt in (("w2d", w2d, (n, k), torch.bfloat16), ("wt2d", wt2d, (k, n), torch.bfloat16),
-                               ("scale", scale, (n,), torch.float32), ("shift", shift, (n,), torch.float32)):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
-            raise ValueError(f"{name} must be a contiguous {shape} {dt} tensor on {x.device}")
+    _check_operands(x.device, ("w2d", w2d, (n, k), torch.bfloat16), ("wt2d", wt2d, (k, n), torch.bfloat16),
+                    ("scale", scale, (n,), torch.float32), ("shift", shift, (n,), torch.float32))
     if res is not None:
         if relu6:
             raise ValueError("a residual input goes with the linear bottleneck only (relu6=False)")
@@ -1216,7 +1195,7 @@ class StemFunction(torch.autograd.Function):
             return (torch.empty((0, 3, h, w), dtype=xdtype, device=g.device),) + (None,) * 6
         p, idx, w_bwd, scale = ctx.saved_tensors
         oh, ow = h // 2, w // 2
-        g = g.to(torch.bfloat16).permute(0, 2, 3, 1).contiguous()   # NHWC (a no-op for channels_last gradients)
+        g = _nhwc_grad(g)                                            # a no-op for channels_last bf16 gradients
         gy = torch.empty((b, oh, ow, 64), dtype=torch.bfloat16, device=g.device)
         _lib.check(lib.adil_stem_pool_bwd(_ptr(g), _ptr(idx), _ptr(p), _ptr(scale), _ptr(gy), b, oh, ow, 64, _stream()),
                    "adil_stem_pool_bwd")
@@ -1278,9 +1257,7 @@ class FirstConv3x3Function(torch.autograd.Function):
         lib = _lib.load()
         w_bwd, scale, y = ctx.saved_tensors
         h, w, xdtype, inv_std, relu6 = ctx.meta
-        g2 = g.permute(0, 2, 3, 1)
-        if not (g2.is_contiguous() and g2.dtype == torch.bfloat16):
-            g2 = g2.to(torch.bfloat16).contiguous()
+        g2 = _nhwc_grad(g)
         b = g2.shape[0]
         gx = torch.empty((b, 3, h, w), dtype=xdtype, device=g2.device)
         if b > 0:
@@ -1297,10 +1274,8 @@ def first_conv3x3(x: Tensor, w_fwd: Tensor, w_bwd: Tensor, scale: Tensor, shift:
         raise ValueError(f"adil_first3x3 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
     if not x.is_contiguous():
         raise ValueError("x must be contiguous (NCHW)")
-    for name, t, shape, dt in (("w_fwd", w_fwd, (32, 48), torch.bfloat16), ("w_bwd", w_bwd, (3, 288), torch.bfloat16),
-                               ("scale", scale, (32,), torch.float32), ("shift", shift, (32,), torch.float32)):
-        if t.dtype != dt or tuple(t.shape) != shape or not t.is_contiguous() or t.device != x.device:
-            raise ValueError(f"{name} must be a contiguous {shape} {dt} tensor on {x.device}")
+    _check_operands(x.device, ("w_fwd", w_fwd, (32, 48), torch.bfloat16), ("w_bwd", w_bwd, (3, 288), torch.bfloat16),
+                    ("scale", scale, (32,), torch.float32), ("shift", shift, (32,), torch.float32))
     mean, inv_std = tuple(float(m) for m in mean), tuple(float(s) for s in inv_std)
     if len(mean) != 3 or len(inv_std) != 3:
         raise ValueError("mean and inv_std must hold three values each")

@@ -16,6 +16,8 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from . import ops
+
 
 class Normalize(nn.Module):
     """(x - mean) / std per channel, the wrapper both reference CLIs put in front of the network
@@ -536,6 +538,36 @@ def canonical_name(name: str) -> str:
 
 
 # ----------------------------------------------------------------------------- frozen-classifier rewrites
+def _bn_scale64(bn: nn.BatchNorm2d) -> torch.Tensor:
+    """gamma / sqrt(var + eps) of an eval-mode BatchNorm in fp64.  The shift that goes with it exists in two orders, and
+    the exact tests pin both: `_bn_affine` (the pointwise, pointwise8, first-convolution, stem and epilogue kernels) rounds
+    this scale to fp32 first and multiplies the running mean by the rounded value; `_OwnDepthwise` (the depthwise
+    kernels) and `fold_batchnorm_` multiply by the fp64 scale and round once at the end."""
+    return bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+
+
+def _plain_conv(conv, k: int, strides, groups: int) -> bool:
+    """A Conv2d of kernel k x k, one of `strides` (both ways), pad (k - 1) / 2, dilation 1, `groups` groups, no bias and
+    zero padding: the geometry the hand-written kernels implement.  Channel conditions are the caller's."""
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (k, k) and conv.stride in [(st, st) for st in strides]
+            and conv.padding == ((k - 1) // 2, (k - 1) // 2) and conv.dilation == (1, 1) and conv.groups == groups
+            and conv.bias is None and conv.padding_mode == 'zeros')
+
+
+def _rewrite_children_(net: nn.Module, match, make, limit: Optional[int] = None) -> int:
+    """Replace every child module of the network (at any depth) for which `match(child)` holds by `make(child)`, at most
+    `limit` of them; returns how many were replaced."""
+    n = 0
+    for parent in list(net.modules()):
+        for name, child in list(parent._modules.items()):
+            if match(child):
+                parent._modules[name] = make(child)
+                n += 1
+                if n == limit:
+                    return n
+    return n
+
+
 def fold_batchnorm_(module: nn.Module) -> nn.Module:
     """Fold every eval-mode BatchNorm2d that directly follows a Conv2d into that convolution (exact in real
     arithmetic: w' = w * gamma/sqrt(var+eps), b' = beta + (b - mean) * gamma/sqrt(var+eps)) and replace the BN by
@@ -550,7 +582,7 @@ def fold_batchnorm_(module: nn.Module) -> nn.Module:
         if not (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d)) or bn.training:
             continue
         with torch.no_grad():
-            scale = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+            scale = _bn_scale64(bn)
             bias = bn.bias.double() - bn.running_mean.double() * scale
             if conv.bias is not None:
                 bias = bias + conv.bias.double() * scale
@@ -597,66 +629,69 @@ class ChannelPaddedConv(nn.Module):
 
 def pad_first_conv_(net: nn.Module, width: int = 8) -> nn.Module:
     """Wrap the network's first 3-channel Conv2d (groups == 1) in a ChannelPaddedConv."""
-    for parent in net.modules():
-        for name, child in parent._modules.items():
-            if isinstance(child, nn.Conv2d) and child.in_channels == 3 and child.groups == 1:
-                parent._modules[name] = ChannelPaddedConv(child, width)
-                return net
+    _rewrite_children_(net, lambda m: isinstance(m, nn.Conv2d) and m.in_channels == 3 and m.groups == 1,
+                       lambda m: ChannelPaddedConv(m, width), limit=1)
     return net
 
 
 def _bn_affine(bn: nn.BatchNorm2d):
     """Eval-mode BatchNorm as a per-channel affine map: y = x * scale + shift (fp32 buffers)."""
     with torch.no_grad():
-        scale = (bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)).float()
+        scale = _bn_scale64(bn).float()
         shift = (bn.bias.double() - bn.running_mean.double() * scale.double()).float()
     return scale.contiguous(), shift.contiguous()
 
 
-class _Fp32Tables(nn.Module):
-    """The per-channel epilogue tables `scale` / `shift` are derived in fp64 and kept in fp32 whatever dtype the
-    network is cast to: `.to(torch.bfloat16)` would otherwise round them to 8 mantissa bits (and a later `.float()`
-    cannot bring the bits back).  They follow device moves only."""
+class _KeepsFp32(nn.Module):
+    """The buffers named in `_KEEP_FP32` are derived in fp64 and kept in fp32 whatever dtype the network is cast to:
+    `.to(torch.bfloat16)` would otherwise round them to 8 mantissa bits (and a later `.float()` cannot bring the bits
+    back).  They follow device moves only.  With `nn.Sequential`, list this class first."""
+    _KEEP_FP32 = ()
 
     def _apply(self, fn, recurse=True):
-        keep = {n: getattr(self, n) for n in ('scale', 'shift')}
+        keep = {n: getattr(self, n) for n in self._KEEP_FP32}
         super()._apply(fn, recurse)
         for n, t in keep.items():
             setattr(self, n, t.to(device=fn(t).device))
         return self
 
 
-class _OwnDepthwise(nn.Sequential):
+class _Fp32Tables(_KeepsFp32):
+    """A layer with the per-channel epilogue tables `scale` / `shift` of `_bn_affine`."""
+    _KEEP_FP32 = ('scale', 'shift')
+
+
+def _init_norm_affine(mod: nn.Module, bn: nn.BatchNorm2d, mean, std, persistent: bool) -> None:
+    """What the input-side kernels (stem, first convolution) take besides their weights: the `Normalize` in front of the
+    network as two float lists `mean` / `inv_std`, and the BatchNorm behind the convolution as `scale` / `shift`."""
+    scale, shift = _bn_affine(bn)
+    mod.register_buffer('scale', scale, persistent=persistent)
+    mod.register_buffer('shift', shift, persistent=persistent)
+    mod.mean = [float(m) for m in mean]
+    mod.inv_std = [1.0 / float(s) for s in std]
+
+
+class _OwnDepthwise(_KeepsFp32, nn.Sequential):
     """A `_ConvBNReLU6` whose convolution is depthwise 3x3 (pad 1, dilation 1, stride 1|2, groups == in == out), run as ONE
     kernel pass (`ops.dw_conv3x3`: convolution, folded eval-BatchNorm and ReLU6) where the kernel covers the input.  The
     original conv / bn / ReLU6 stay as submodules '0' / '1' / '2' (same state_dict keys; they serve every other input: CPU,
-    fp32, not channels_last).  The folded tables `w9c` [9][C] and `bias` [C] are derived in fp64 from the weights the block
-    holds when it is rewritten, kept fp32 under `.to(bfloat16)` like `_Fp32Tables`, follow device moves, and are not part
-    of the state_dict."""
-    _TABLES = ('w9c', 'bias')
+    fp32, not channels_last).  The folded tables `w9c` [9][C] and `bias` [C] come from the weights the block holds when it
+    is rewritten and are not part of the state_dict."""
+    _KEEP_FP32 = ('w9c', 'bias')
 
     def __init__(self, block: _ConvBNReLU6):
         super().__init__(*block.children())
         conv, bn = self[0], self[1]
         if not _is_depthwise3x3(block):
             raise ValueError("not a depthwise 3x3 conv + BatchNorm + ReLU6 block")
-        from . import ops
         with torch.no_grad():            # the whole fold in fp64, one rounding to fp32 per table entry
-            scale64 = bn.weight.double() / torch.sqrt(bn.running_var.double() + bn.eps)
+            scale64 = _bn_scale64(bn)
             shift = (bn.bias.double() - bn.running_mean.double() * scale64).float().contiguous()
         self.channels, self.stride = conv.out_channels, conv.stride[0]
         self.register_buffer('w9c', ops.pack_dw3x3_weights(conv.weight, scale64), persistent=False)
         self.register_buffer('bias', shift, persistent=False)
 
-    def _apply(self, fn, recurse=True):
-        keep = {n: getattr(self, n) for n in self._TABLES}
-        super()._apply(fn, recurse)
-        for n, t in keep.items():
-            setattr(self, n, t.to(device=fn(t).device))
-        return self
-
     def forward(self, x):
-        from . import ops
         if (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and ops.dw_conv3x3_covers(x, self.channels)
                 and x.is_contiguous(memory_format=torch.channels_last) and self.w9c.device == x.device):
             return ops.dw_conv3x3(x, self.w9c, self.bias, self.stride, True)
@@ -667,40 +702,29 @@ def _is_depthwise3x3(block) -> bool:
     if not isinstance(block, _ConvBNReLU6) or len(block) != 3:
         return False
     conv, bn = block[0], block[1]
-    return (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and conv.kernel_size == (3, 3)
-            and conv.padding == (1, 1) and conv.dilation == (1, 1) and conv.stride in ((1, 1), (2, 2))
-            and conv.groups == conv.in_channels == conv.out_channels and conv.bias is None
-            and conv.padding_mode == 'zeros')
+    return (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and _plain_conv(conv, 3, (1, 2), conv.in_channels)
+            and conv.in_channels == conv.out_channels)
 
 
 def use_own_depthwise_(net: nn.Module) -> int:
     """Replace every depthwise 3x3 `_ConvBNReLU6` of the network by an `_OwnDepthwise`; returns how many were replaced."""
-    n = 0
-    for parent in list(net.modules()):
-        for name, child in list(parent._modules.items()):
-            if _is_depthwise3x3(child) and not isinstance(child, _OwnDepthwise):
-                parent._modules[name] = _OwnDepthwise(child)
-                n += 1
-    return n
+    return _rewrite_children_(net, _is_depthwise3x3, _OwnDepthwise)
 
 
 def _is_pointwise(conv, bn) -> bool:
-    return (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and conv.kernel_size == (1, 1)
-            and conv.stride == (1, 1) and conv.padding == (0, 0) and conv.dilation == (1, 1) and conv.groups == 1
-            and conv.bias is None and conv.in_channels % 8 == 0 and conv.out_channels % 8 == 0
-            and 8 <= conv.in_channels <= 2048 and 8 <= conv.out_channels <= 2048)
+    return (_plain_conv(conv, 1, (1,), 1) and isinstance(bn, nn.BatchNorm2d) and conv.in_channels in ops.PW8_CHANNELS
+            and conv.out_channels in ops.PW8_CHANNELS)
 
 
 def _is_pointwise_block(block) -> bool:
     return isinstance(block, _ConvBNReLU6) and len(block) == 3 and _is_pointwise(block[0], block[1])
 
 
-class _Pw8Tables(nn.Module):
+class _Pw8Tables(_KeepsFp32):
     """What `ops.pw8_conv` needs of one 1x1 convolution + eval-BatchNorm, as non-persistent buffers (no state_dict
-    entries): `scale` / `shift` [N], derived in fp64 as `_bn_affine` derives them and kept fp32 under `.to(bfloat16)`;
-    `wt2d` [K][N], the transposed weight, which is cast with the network (its bf16 rounding is the weight's own).  The
-    [N][K] weight is the convolution's own storage."""
-    _TABLES = ('scale', 'shift')
+    entries): `scale` / `shift` [N] of `_bn_affine`; `wt2d` [K][N], the transposed weight, which is cast with the network
+    (its bf16 rounding is the weight's own).  The [N][K] weight is the convolution's own storage."""
+    _KEEP_FP32 = ('scale', 'shift')
 
     def _init_tables(self, conv, bn):
         scale, shift = _bn_affine(bn)
@@ -709,21 +733,12 @@ class _Pw8Tables(nn.Module):
         self.register_buffer('shift', shift, persistent=False)
         self.register_buffer('wt2d', conv.weight.detach().reshape(self.cout, self.cin).t().contiguous(), persistent=False)
 
-    def _apply(self, fn, recurse=True):
-        keep = {n: getattr(self, n) for n in self._TABLES}
-        super()._apply(fn, recurse)
-        for n, t in keep.items():
-            setattr(self, n, t.to(device=fn(t).device))
-        return self
-
     def _covers(self, x, conv):
-        from . import ops
         return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and ops.pw8_conv_covers(x, self.cin, self.cout)
                 and x.is_contiguous(memory_format=torch.channels_last) and conv.weight.dtype == torch.bfloat16
                 and self.wt2d.dtype == torch.bfloat16 and self.wt2d.device == x.device and self.scale.device == x.device)
 
     def _pw8(self, x, conv, res, relu6):
-        from . import ops
         w2d = conv.weight.reshape(self.cout, self.cin)
         if not w2d.is_contiguous():
             w2d = w2d.contiguous()
@@ -781,63 +796,42 @@ def use_own_pointwise_(net: nn.Module) -> int:
     """Replace every 1x1 `_ConvBNReLU6` of the network by an `_OwnPointwise` and every `_InvertedResidual` by an
     `_OwnInvertedResidual`; returns how many 1x1 layers were rewritten (MobileNetV2: 16 expansions, 17 projections and
     the 320 -> 1280 layer)."""
-    n = 0
-    for parent in list(net.modules()):
-        for name, child in list(parent._modules.items()):
-            if _is_pointwise_block(child):
-                parent._modules[name] = _OwnPointwise(child)
-                n += 1
-            elif _is_projection_block(child):
-                parent._modules[name] = _OwnInvertedResidual(child)
-                n += 1
-    return n
+    return (_rewrite_children_(net, _is_pointwise_block, _OwnPointwise)
+            + _rewrite_children_(net, _is_projection_block, _OwnInvertedResidual))
 
 
 def _is_first_conv_block(block) -> bool:
     if not isinstance(block, _ConvBNReLU6) or len(block) != 3:
         return False
     conv, bn = block[0], block[1]
-    return (isinstance(conv, nn.Conv2d) and isinstance(bn, nn.BatchNorm2d) and conv.in_channels == 3
-            and conv.out_channels == 32 and conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1)
-            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None and conv.padding_mode == 'zeros')
+    return (_plain_conv(conv, 3, (2,), 1) and isinstance(bn, nn.BatchNorm2d) and conv.in_channels == 3
+            and conv.out_channels == 32)
 
 
-class _OwnFirstConv(nn.Sequential):
+class _OwnFirstConv(_KeepsFp32, nn.Sequential):
     """`features[0]` of MobileNetV2 (a `_ConvBNReLU6` with conv 3 -> 32, 3x3, stride 2, pad 1, groups 1, no bias) together
     with the `Normalize` in front of the network, run as ONE kernel pass (`ops.first_conv3x3`) on the attack's own
     (B,3,H,W) fp32 / bf16 tensor where the kernel covers the input; its backward produces dLoss/dx in the layout
     `adil_grad` reads.  The original conv / bn / ReLU6 stay as submodules '0' / '1' / '2' (same state_dict keys); on every
     other input (CPU, fp32 network, wrong channel count) the module normalises in torch exactly as `Normalize` does and
     runs them, so the rewritten network is the same function everywhere.  Non-persistent buffers (no state_dict
-    entries): `scale` / `shift` from `_bn_affine`, kept fp32 under `.to(bfloat16)` and following device moves; the packed
-    weights `w_fwd` / `w_bwd` and the `Normalize` tables `norm_mean` / `norm_std`, cast with the network.  The kernel takes
-    `mean` and `inv_std` as plain floats."""
-    _TABLES = ('scale', 'shift')
+    entries): `scale` / `shift` from `_bn_affine`; the packed weights `w_fwd` / `w_bwd` and the `Normalize` tables
+    `norm_mean` / `norm_std`, cast with the network.  The kernel takes `mean` and `inv_std` as plain floats."""
+    _KEEP_FP32 = ('scale', 'shift')
 
     def __init__(self, block: _ConvBNReLU6, mean, std):
         super().__init__(*block.children())
         if not _is_first_conv_block(block):
             raise ValueError("not a 3 -> 32, 3x3, stride 2, pad 1 conv + BatchNorm + ReLU6 block")
-        from . import ops
         conv, bn = self[0], self[1]
         w_fwd, w_bwd = ops.pack_first3x3_weights(conv.weight)
-        scale, shift = _bn_affine(bn)
-        self.mean = [float(m) for m in mean]
-        self.inv_std = [1.0 / float(s) for s in std]
-        for name, t in (('scale', scale), ('shift', shift), ('w_fwd', w_fwd), ('w_bwd', w_bwd),
+        _init_norm_affine(self, bn, mean, std, persistent=False)
+        for name, t in (('w_fwd', w_fwd), ('w_bwd', w_bwd),
                         ('norm_mean', torch.tensor(self.mean, dtype=torch.float32, device=conv.weight.device)),
                         ('norm_std', torch.tensor([float(v) for v in std], dtype=torch.float32, device=conv.weight.device))):
             self.register_buffer(name, t, persistent=False)
 
-    def _apply(self, fn, recurse=True):
-        keep = {n: getattr(self, n) for n in self._TABLES}
-        super()._apply(fn, recurse)
-        for n, t in keep.items():
-            setattr(self, n, t.to(device=fn(t).device))
-        return self
-
     def forward(self, x):
-        from . import ops
         if (ops.first_conv3x3_covers(x) and self[0].weight.dtype == torch.bfloat16 and self.w_fwd.dtype == torch.bfloat16
                 and self.w_fwd.device == x.device and self.scale.device == x.device):
             return ops.first_conv3x3(x.contiguous(), self.w_fwd, self.w_bwd, self.scale, self.shift, self.mean,
@@ -871,24 +865,18 @@ class _ConvAffine(_Fp32Tables):
         self.pointwise_s2 = one_by_one and conv.stride == (2, 2)         # the ResNet downsample convolutions
         if one_by_one:          # (Cin, Cout) copy for the input-gradient kernel; 2-D, so channels_last leaves it alone
             self.register_buffer('wt2d', conv.weight.detach().reshape(conv.out_channels, conv.in_channels).t().contiguous())
-        self.dense3x3 = (conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
-                         and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-                         and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0)
+        self.dense3x3 = _plain_conv(conv, 3, (1,), 1) and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
         if self.dense3x3:
-            from . import ops
             wp_fwd, wp_bwd = ops.pack_conv3x3_weights(conv.weight)
             self.register_buffer('wp_fwd', wp_fwd)
             self.register_buffer('wp_bwd', wp_bwd)
         # the stride-2 3x3 layers (conv2 of the first bottleneck of stages 2-4, conv1 of the same BasicBlocks)
-        self.dense3x3_s2 = (conv.kernel_size == (3, 3) and conv.stride == (2, 2) and conv.padding == (1, 1)
-                            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is None
-                            and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0)
+        self.dense3x3_s2 = _plain_conv(conv, 3, (2,), 1) and conv.in_channels % 64 == 0 and conv.out_channels % 64 == 0
         self.own_strided_conv = False    # set by use_own_strided_conv_ (FusedResNet(own_strided_conv=True))
 
     def use_own_strided_conv_(self):
         """Route a dense stride-2 3x3 layer to ops.conv3x3_s2 where the kernel covers the input (weights packed once)."""
         if self.dense3x3_s2 and not self.own_strided_conv:
-            from . import ops
             wp_fwd, wp_bwd = ops.pack_conv3x3_s2_weights(self.conv.weight)
             self.register_buffer('wp_s2_fwd', wp_fwd.to(self.conv.weight.device))
             self.register_buffer('wp_s2_bwd', wp_bwd.to(self.conv.weight.device))
@@ -898,10 +886,8 @@ class _ConvAffine(_Fp32Tables):
     def raw_conv(self, x):
         """The convolution alone (no BatchNorm / ReLU): the hand-written 3x3 kernels where they apply, else the library."""
         if self.dense3x3 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[-1] <= 63:   # kernel limit: W <= 63
-            from . import ops
             return ops.conv3x3(x, self.wp_fwd, self.wp_bwd)
         if self.own_strided_conv and self.wp_s2_fwd.dtype == torch.bfloat16:
-            from . import ops
             if ops.conv3x3_s2_covers(x, self.conv.in_channels, self.conv.out_channels):
                 return ops.conv3x3_s2(x, self.wp_s2_fwd, self.wp_s2_bwd)
         return self.conv(x)
@@ -930,7 +916,6 @@ class _ConvAffine(_Fp32Tables):
         """outputs = 2 / 3: the result twice (+ its [:, :, ::2, ::2] view); pre=(scale, shift) of the previous layer
         means x is that layer's RAW convolution output; strided_view: x is a [:, :, ::2, ::2] view for a stride-2 1x1
         convolution (see ops.PointwiseConvFunction).  All only with the fused kernels."""
-        from . import ops
         if self.fused_pointwise(x) or (strided_view and self.fused_pointwise_s2(x)):
             w2d = self.conv.weight.reshape(self.conv.out_channels, self.conv.in_channels)
             if w2d.is_contiguous():                                      # (Cout, Cin): true for either memory format
@@ -959,7 +944,6 @@ class _FusedResBlock(nn.Module):
     def joins(self, nxt) -> bool:
         """This block's conv3 and `nxt`'s conv1 can run as one residual-join kernel (ops.PointwiseJoinFunction): two
         bottlenecks of one stage (nxt has no downsample) at a width the join kernels cover."""
-        from . import ops
         return (self.bottleneck and nxt.bottleneck and nxt.down is None and not self.emit_sub
                 and self.c3.pointwise and nxt.c1.pointwise and self.c3.conv.in_channels in ops.JOIN_WIDTHS
                 and nxt.c1.conv.out_channels == self.c3.conv.in_channels
@@ -989,7 +973,6 @@ class _FusedResBlock(nn.Module):
             if (self.c2.relu and self.c3.fused_pointwise(raw) and self.c3.conv.in_channels <= 512
                     and raw.is_contiguous(memory_format=torch.channels_last)):
                 if nxt is not None and idt.dtype == torch.bfloat16:
-                    from . import ops
                     c3, c1 = self.c3, nxt.c1
                     w3 = c3.conv.weight.reshape(c3.conv.out_channels, c3.conv.in_channels)
                     w1 = c1.conv.weight.reshape(c1.conv.out_channels, c1.conv.in_channels)
@@ -997,7 +980,6 @@ class _FusedResBlock(nn.Module):
                         return _Joined(*ops.pointwise_join(raw, idt, w3, c3.wt2d, (self.c2.scale, self.c2.shift), c3.scale,
                                                            c3.shift, w1, c1.wt2d, c1.scale, c1.shift))
                 return self.c3(raw, res=idt, outputs=n_out, pre=(self.c2.scale, self.c2.shift))   # bn2+ReLU run inside c3
-            from . import ops
             out = ops.affine_act(raw, self.c2.scale.float(), self.c2.shift.float(), relu=self.c2.relu)
             return self.c3(out, res=idt, outputs=n_out)
         return self.c2(out, res=idt)
@@ -1016,41 +998,29 @@ class _FusedStem(_Fp32Tables):
 
     def __init__(self, conv: nn.Conv2d, bn: nn.BatchNorm2d, mean, std):
         super().__init__()
-        from . import ops
         if conv.bias is not None or conv.stride != (2, 2) or conv.padding != (3, 3):
             raise ValueError("stem kernels implement the torchvision ResNet conv1 (7x7, stride 2, padding 3, no bias)")
         w_fwd, w_bwd = ops.pack_stem_weights(conv.weight)
-        scale, shift = _bn_affine(bn)
         self.register_buffer('w_fwd', w_fwd)
         self.register_buffer('w_bwd', w_bwd)
-        self.register_buffer('scale', scale)
-        self.register_buffer('shift', shift)
-        self.mean = [float(m) for m in mean]
-        self.inv_std = [1.0 / float(s) for s in std]
+        _init_norm_affine(self, bn, mean, std, persistent=True)
 
     def forward(self, x):
-        from . import ops
         return ops.resnet_stem(x, self.w_fwd, self.w_bwd, self.scale, self.shift, self.mean, self.inv_std)
 
 
-class _Fp32Head(nn.Module):
+class _Fp32Head(_KeepsFp32):
     """Global average pool + the last linear layer in fp32, whatever dtype the network is cast to: the weights keep their
-    fp32 bits (like _Fp32Tables), the pooled features are widened before the layer, the logits come out fp32.
+    fp32 bits (`_KeepsFp32`), the pooled features are widened before the layer, the logits come out fp32.
     Why (round 4, VERDICT r3 #1c): a bf16 head rounds logits of magnitude 16-64 to steps of 0.125-0.25, which is the scale
     on which the attack's argmax decisions ("fooled") and its margin loss are taken; the head is 2 MFLOP per image next to
     the backbone's 4 GFLOP, so keeping it fp32 costs nothing measurable.  The backbone stays bf16."""
+    _KEEP_FP32 = ('weight', 'bias')
 
     def __init__(self, fc: nn.Linear):
         super().__init__()
         self.register_buffer('weight', fc.weight.detach().float().clone())
         self.register_buffer('bias', fc.bias.detach().float().clone() if fc.bias is not None else torch.zeros(fc.out_features))
-
-    def _apply(self, fn, recurse=True):
-        keep = {n: getattr(self, n) for n in ('weight', 'bias')}
-        super()._apply(fn, recurse)
-        for n, t in keep.items():
-            setattr(self, n, t.to(device=fn(t).device))
-        return self
 
     def forward(self, x):
         return F.linear(x.float().mean(dim=(2, 3)), self.weight, self.bias)
@@ -1191,24 +1161,15 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     if own_strided_conv and not fuse_bn_act:
         raise ValueError("own_strided_conv is a switch of the FusedResNet path (fuse_bn_act=True)")
     key = canonical_name(name)
-    if own_depthwise and key != 'mobilenet_v2':
-        raise ValueError("own_depthwise is a switch of MobileNetV2 (the depthwise 3x3 layers of no other network are covered)")
-    if own_depthwise and dtype != torch.bfloat16:
-        raise ValueError("own_depthwise needs a bfloat16 network (the depthwise kernels read and write bf16 activations)")
-    if own_depthwise and not channels_last:
-        raise ValueError("own_depthwise needs channels_last=True (the depthwise kernels work on channels_last storage)")
-    if own_pointwise and key != 'mobilenet_v2':
-        raise ValueError("own_pointwise is a switch of MobileNetV2 (the 1x1 layers of no other network are rewritten)")
-    if own_pointwise and dtype != torch.bfloat16:
-        raise ValueError("own_pointwise needs a bfloat16 network (the pointwise kernels read and write bf16 activations)")
-    if own_pointwise and not channels_last:
-        raise ValueError("own_pointwise needs channels_last=True (the pointwise kernels work on channels_last storage)")
-    if own_first_conv and key != 'mobilenet_v2':
-        raise ValueError("own_first_conv is a switch of MobileNetV2 (the first convolution of no other network is rewritten)")
-    if own_first_conv and dtype != torch.bfloat16:
-        raise ValueError("own_first_conv needs a bfloat16 network (the first-convolution kernels write bf16 activations)")
-    if own_first_conv and not channels_last:
-        raise ValueError("own_first_conv needs channels_last=True (the first-convolution kernels write channels_last storage)")
+    for switch, on, kernels, layers in (('own_depthwise', own_depthwise, 'depthwise', 'the depthwise 3x3 layers'),
+                                        ('own_pointwise', own_pointwise, 'pointwise', 'the 1x1 layers'),
+                                        ('own_first_conv', own_first_conv, 'first-convolution', 'the first convolution')):
+        if on and key != 'mobilenet_v2':
+            raise ValueError(f"{switch} is a switch of MobileNetV2 (no other network has {layers} rewritten)")
+        if on and dtype != torch.bfloat16:
+            raise ValueError(f"{switch} needs a bfloat16 network (the {kernels} kernels work on bf16 activations)")
+        if on and not channels_last:
+            raise ValueError(f"{switch} needs channels_last=True (the {kernels} kernels work on channels_last storage)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)

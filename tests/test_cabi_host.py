@@ -208,6 +208,39 @@ def test_epilogue_tables_stay_fp32_under_dtype_casts():
     tables = [m for m in fused.modules() if isinstance(m, zoo._Fp32Tables)]
     assert len(tables) > 10 and all(m.scale.dtype == m.shift.dtype == torch.float32 for m in tables)
     assert all(p.dtype == torch.bfloat16 for p in fused.parameters())
+    # every class that declares protected buffers keeps them through the one `_apply` of zoo._KeepsFp32
+    mean, std = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
+    res = zoo.ResNet(zoo.Bottleneck, [1, 1, 1, 1])
+    mob = zoo.MobileNetV2(10)
+    for m in list(res.modules()) + list(mob.modules()):
+        if isinstance(m, torch.nn.BatchNorm2d):
+            m.running_var.copy_(0.5 + torch.rand(m.running_var.shape, generator=g))
+            m.running_mean.copy_(torch.randn(m.running_mean.shape, generator=g))
+            m.weight.data.copy_(0.5 + torch.rand(m.weight.shape, generator=g))
+            m.bias.data.copy_(torch.randn(m.bias.shape, generator=g))
+    assert zoo.use_own_depthwise_(mob) == 17 and zoo.use_own_pointwise_(mob) == 34
+    assert zoo.use_own_first_conv_(mob, mean, std) == 1
+    nets = [zoo.FusedResNet(res, normalize=(mean, std), head_fp32=True), zoo.FusedResNet(res, head_fp32=True), mob]
+    keepers = [m for net in nets for m in net.modules() if isinstance(m, zoo._KeepsFp32)]
+    assert {type(m) for m in keepers} == {zoo._ConvAffine, zoo._FusedStem, zoo._Fp32Head, zoo._OwnDepthwise,
+                                          zoo._OwnPointwise, zoo._OwnInvertedResidual, zoo._OwnFirstConv}
+    for m in keepers:
+        owners = [c for c in type(m).__mro__ if "_apply" in vars(c)]
+        assert owners == [zoo._KeepsFp32, torch.nn.Module], type(m)
+        assert len(m._KEEP_FP32) == 2, type(m)
+    built = [{n: getattr(m, n).clone() for n in m._KEEP_FP32} for m in keepers]
+    assert all(t.dtype == torch.float32 for want in built for t in want.values())
+    for cast in (lambda net: net.to(torch.bfloat16), lambda net: net.float().to(torch.bfloat16),
+                 lambda net: net.to(memory_format=torch.channels_last)):
+        for net in nets:
+            cast(net)
+        for m, want in zip(keepers, built):
+            for n, t in want.items():
+                got = getattr(m, n)
+                assert got.dtype == torch.float32 and torch.equal(got, t), (type(m), n)
+        assert all(p.dtype == torch.bfloat16 for net in nets for p in net.parameters())
+    # the protection is worth something here: a plain cast would have changed these tables
+    assert any(not torch.equal(t.to(torch.bfloat16).float(), t) for want in built for t in want.values())
 
 
 def test_shuffled_batches_follow_the_reference_dataloader():
@@ -462,3 +495,27 @@ def test_fp32_head_keeps_its_bits_and_the_switch_restores():
     import pytest
     with pytest.raises(ValueError):
         zoo.FusedResNet(zoo._BUILDERS["resnet18"](10), head_fp32="sometimes")
+
+
+def test_nhwc_helpers_copy_only_when_they_must():
+    """ops._nhwc / ops._nhwc_grad hand the kernels an NHWC tensor.  A copy or a cast that is not needed changes no
+    result, so no exact test sees it: the storage is compared here."""
+    from dl_attack_on_imagenet_amd import ops
+    x = torch.randn(2, 8, 3, 5, generator=torch.Generator().manual_seed(0))
+    cl = x.contiguous(memory_format=torch.channels_last)
+    v = ops._nhwc(cl)                                            # channels_last: the view, no copy
+    assert v.shape == (2, 3, 5, 8) and v.is_contiguous() and v.data_ptr() == cl.data_ptr()
+    c = ops._nhwc(x)                                             # NCHW: one NHWC copy
+    assert c.shape == (2, 3, 5, 8) and c.is_contiguous() and c.data_ptr() != x.data_ptr()
+    assert c.dtype == x.dtype and torch.equal(c, x.permute(0, 2, 3, 1))
+    g = cl.to(torch.bfloat16)
+    assert g.is_contiguous(memory_format=torch.channels_last)
+    gv = ops._nhwc_grad(g)                                       # channels_last bf16: the view, no cast, no copy
+    assert gv.dtype == torch.bfloat16 and gv.shape == (2, 3, 5, 8) and gv.is_contiguous() and gv.data_ptr() == g.data_ptr()
+    bits = x.permute(0, 2, 3, 1).contiguous().view(torch.int32)  # round to nearest even on the fp32 bit patterns
+    want = (((bits + 0x7FFF + ((bits >> 16) & 1)) >> 16) << 16).view(torch.float32).to(torch.bfloat16)
+    assert torch.equal(want.float().view(torch.int32) & 0xFFFF, torch.zeros_like(bits))
+    for arg in (cl, x.to(torch.bfloat16)):                       # fp32 channels_last, bf16 NCHW
+        got = ops._nhwc_grad(arg)
+        assert got.dtype == torch.bfloat16 and got.shape == (2, 3, 5, 8) and got.is_contiguous()
+        assert got.data_ptr() != arg.data_ptr() and torch.equal(got, want)
