@@ -77,6 +77,12 @@ def build_parser():
                         'and ReLU6) run in the first-convolution kernels on the attack\'s own tensors; 0 (default) = the '
                         'library.  Independent of the other two; with all three no library convolution is left.  Ignored '
                         'otherwise')
+    p.add_argument('--own-head', default='0', choices=['0', 'inference', 'always'],
+                   help='-m mobilenet --dtype bf16: global pooling + the last linear layer in the pooled-head kernels with '
+                        'fp32 logits on channels_last storage; inference = only inside the DDrague inference loop '
+                        '(engine.precise_head), always = in every classifier call; 0 (default) = the library pooling and '
+                        'bf16 linear layer.  Independent of the other three; with all four no library call is left in the '
+                        'classifier.  Ignored otherwise')
     return p
 
 
@@ -139,11 +145,13 @@ def main(args):
     mobile_bf16 = dtype == torch.bfloat16 and zoo.canonical_name(model_name) == 'mobilenet_v2'
     own_dw, own_pw = bool(args.own_depthwise) and mobile_bf16, bool(args.own_pointwise) and mobile_bf16
     own_fc = bool(args.own_first_conv) and mobile_bf16
+    own_head = {'0': False, 'inference': 'inference', 'always': True}[args.own_head] if mobile_bf16 else False
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
-                                 channels_last=fast or own_dw or own_pw or own_fc, own_depthwise=own_dw, own_pointwise=own_pw,
+                                 channels_last=fast or own_dw or own_pw or own_fc or bool(own_head), own_depthwise=own_dw,
+                                 own_pointwise=own_pw,
                                  own_first_conv=own_fc, fuse_bn_act=fast,
                                  fuse_stem=fast,
-                                 head_fp32="inference" if fast else False,      # fp32 logits inside the DDrague inference loop
+                                 head_fp32="inference" if fast else own_head,   # fp32 logits inside the DDrague inference loop
                                  own_strided_conv=fast and bool(args.own_strided_conv))
     if args.clean_accuracy:                                                               # demo_dL_attack.py:65-66
         from model_accuracy import model_accuracy, model_accuracy_distributed

@@ -1283,6 +1283,72 @@ def first_conv3x3(x: Tensor, w_fwd: Tensor, w_bwd: Tensor, scale: Tensor, shift:
 
 
 # --------------------------------------------------------------------------- #
+POOL_HEAD_CHANNELS = range(8, 2048 + 1, 8)   # channel counts of adil_pool_head_fwd / _bwd (include/adil_hip.h)
+POOL_HEAD_MAX_PIXELS = 65536
+POOL_HEAD_MAX_BATCH = 65535                  # the image index is a grid dimension
+POOL_HEAD_MAX_CLASSES = 65535
+
+
+def pool_head_covers(x: Tensor, C: int) -> bool:
+    """What adil_pool_head_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the torch formula)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == C and C in POOL_HEAD_CHANNELS
+            and 1 <= x.shape[2] * x.shape[3] <= POOL_HEAD_MAX_PIXELS and x.shape[0] <= POOL_HEAD_MAX_BATCH
+            and x.is_contiguous(memory_format=torch.channels_last))
+
+
+class PoolHeadFunction(torch.autograd.Function):
+    """Global average pool + linear layer with fp32 logits on a channels_last bf16 activation (adil_pool_head_fwd: one
+    pass over x, one fp32 GEMM); the input gradient is the fp32 GEMM against the weight and one broadcast pass that
+    writes the bf16 gradient (adil_pool_head_bwd).  The pooled features and their gradient are fp32 tensors from the
+    torch allocator (the call is capturable).  No weight gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, w, wt, bias):
+        lib = _lib.load()
+        b, c, h, wd = x.shape
+        n = w.shape[0]
+        x2 = _nhwc(x)
+        pooled = torch.empty((b, c), dtype=torch.float32, device=x.device)
+        logits = torch.empty((b, n), dtype=torch.float32, device=x.device)
+        if b > 0:
+            _lib.check(lib.adil_pool_head_fwd(_ptr(x2), _ptr(wt), _ptr(bias), _ptr(pooled), _ptr(logits), b, h * wd, c, n,
+                                              _stream()), "adil_pool_head_fwd")
+        ctx.save_for_backward(w)
+        ctx.meta = (b, c, h, wd)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        w, = ctx.saved_tensors
+        b, c, h, wd = ctx.meta
+        n = w.shape[0]
+        if g.dtype != torch.float32 or tuple(g.shape) != (b, n):
+            raise ValueError(f"the logit gradient must be a float32 {(b, n)} tensor, got {g.dtype} {tuple(g.shape)}")
+        g2 = g if g.is_contiguous() else g.contiguous()
+        gpooled = torch.empty((b, c), dtype=torch.float32, device=g2.device)
+        gx = torch.empty((b, h, wd, c), dtype=torch.bfloat16, device=g2.device)
+        if b > 0:
+            _lib.check(lib.adil_pool_head_bwd(_ptr(g2), _ptr(w), _ptr(gpooled), _ptr(gx), b, h * wd, c, n, _stream()),
+                       "adil_pool_head_bwd")
+        return gx.permute(0, 3, 1, 2), None, None, None
+
+
+def pool_head(x: Tensor, w: Tensor, wt: Tensor, bias: Tensor) -> Tensor:
+    """x (B,C,H,W) bf16 in channels_last memory format -> mean over (H,W) . w^T + bias as fp32 (B,N) logits, no copy of
+    x.  w (N,C), its transpose wt (C,N) and bias (N,) are fp32."""
+    if w.dim() != 2:
+        raise ValueError(f"w must be a (N, C) matrix, got {tuple(w.shape)}")
+    n, c = w.shape
+    if not pool_head_covers(x, c) or not 1 <= n <= POOL_HEAD_MAX_CLASSES:
+        raise ValueError(f"adil_pool_head does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with a {n} x {c} "
+                         "weight (bf16, channels_last)")
+    _check_operands(x.device, ("w", w, (n, c), torch.float32), ("wt", wt, (c, n), torch.float32),
+                    ("bias", bias, (n,), torch.float32))
+    return PoolHeadFunction.apply(x, w, wt, bias)
+
+
+# --------------------------------------------------------------------------- #
 class DictSynthFunction(torch.autograd.Function):
     """x + D v[index] as a differentiable op (the tensordot of adil.py:25 and its autograd backward).
     grad wrt v is dense (N,K) with zero rows outside `index`, exactly what autograd produces."""

@@ -275,10 +275,22 @@ class MobileNetV2(nn.Module):
         feats.append(_ConvBNReLU6(inp, 1280, 1))
         self.features = nn.Sequential(*feats)
         self.classifier = nn.Sequential(nn.Dropout(0.2), nn.Linear(1280, num_classes))
+        self.head32, self.head32_on = None, False        # an `_OwnHead`, attached by use_own_head_
 
     def forward(self, x):
-        x = F.adaptive_avg_pool2d(self.features(x), 1)
+        x = self.features(x)
+        if self.head32 is not None and self.head32_on:
+            return self.head32(x)
+        x = F.adaptive_avg_pool2d(x, 1)
         return self.classifier(torch.flatten(x, 1))
+
+    def precise_head(self, enabled: bool) -> bool:
+        """Switch the fp32 head on / off (networks rewritten by use_own_head_(net, "inference")); returns the previous
+        state.  The protocol of `FusedResNet.precise_head`, which is what engine.precise_head looks for."""
+        prev = self.head32_on
+        if self.head32 is not None:
+            self.head32_on = bool(enabled)
+        return prev
 
 
 class VGG11(nn.Module):
@@ -1026,6 +1038,42 @@ class _Fp32Head(_KeepsFp32):
         return F.linear(x.float().mean(dim=(2, 3)), self.weight, self.bias)
 
 
+class _OwnHead(_Fp32Head):
+    """`_Fp32Head` as ONE kernel pass each way (`ops.pool_head`: a single read of the bf16 channels_last activation, an
+    fp32 GEMM, fp32 logits; the backward writes the bf16 gradient once) where the kernels cover the input.  It holds the
+    Linear's `weight` [N][C] and `bias` as `_Fp32Head` does plus the transpose `wt` [C][N] that the forward reads, all
+    fp32 whatever the network is cast to and all NON-persistent: the Linear itself stays in the network under its own
+    names, so the state_dict has the plain network's keys.  On every other input (CPU, fp32 activations, not
+    channels_last) `_Fp32Head.forward` runs unchanged: the rewritten network is the same function everywhere."""
+    _KEEP_FP32 = ('weight', 'bias', 'wt')
+
+    def __init__(self, fc: nn.Linear):
+        super().__init__(fc)
+        for name in ('weight', 'bias'):                  # `_Fp32Head` registered them as persistent buffers
+            self.register_buffer(name, getattr(self, name), persistent=False)
+        self.register_buffer('wt', self.weight.t().contiguous(), persistent=False)
+
+    def forward(self, x):
+        if (ops.pool_head_covers(x, self.weight.shape[1]) and self.weight.device == x.device and self.wt.device == x.device
+                and self.bias.device == x.device):
+            return ops.pool_head(x, self.weight, self.wt, self.bias)
+        return super().forward(x)
+
+
+def use_own_head_(net: nn.Module, mode=True) -> int:
+    """Attach an `_OwnHead` built from the last Linear of a MobileNetV2 (after its weights are loaded) and route the
+    network's forward through it: `mode` True = always, "inference" = only while `precise_head(True)` is in force
+    (engine.precise_head, the DDrague inference solver).  `classifier` stays in place under its names and serves the
+    network whenever the head is off.  Returns how many heads were attached (1)."""
+    if mode not in (True, "inference"):
+        raise ValueError("the own head's mode must be True or 'inference'")
+    if not isinstance(net, MobileNetV2) or not isinstance(net.classifier[-1], nn.Linear):
+        raise ValueError("the own head rewrites the pooling + classifier of MobileNetV2")
+    net.head32 = _OwnHead(net.classifier[-1])
+    net.head32_on = mode is True
+    return 1
+
+
 class FusedResNet(nn.Module):
     """A frozen ResNet whose BatchNorm(eval) / residual add / ReLU run as ONE elementwise kernel per convolution
     (`ops.affine_act`, forward and input-gradient backward) instead of 2-3 separate PyTorch kernels.  Convolution
@@ -1147,20 +1195,29 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
     normalisation and the first stage into the stem kernels (the Sequential then holds the network alone); head_fp32
-    (with fuse_bn_act) keeps global pooling + the last linear layer in fp32 under a bf16 cast (fp32 logits): True = always,
-    "inference" = only inside engine.precise_head (the DDrague inference solver), see FusedResNet; own_strided_conv (with
-    fuse_bn_act) runs the stride-2 3x3 convolutions in the hand-written kernel instead of the library (off by default);
+    (with fuse_bn_act, or MobileNetV2 in bf16 + channels_last, where it is the pooled-head kernel pair of `_OwnHead`,
+    independent of the three own_* switches) keeps global pooling + the last linear layer in fp32 under a bf16 cast (fp32
+    logits): True = always, "inference" = only inside engine.precise_head (the DDrague inference solver), see FusedResNet;
+    own_strided_conv (with fuse_bn_act) runs the stride-2 3x3 convolutions in the hand-written kernel instead of the
+    library (off by default);
     own_depthwise (MobileNetV2, bf16, channels_last) runs the 17 depthwise 3x3 layers with their BatchNorm and ReLU6 in
     the hand-written kernel (`_OwnDepthwise`; off by default); own_pointwise (same conditions, independent of
     own_depthwise) runs the 34 1x1 layers with their BatchNorm, ReLU6 and residual add in the narrow-channel GEMM kernel
     (`_OwnPointwise` / `_OwnInvertedResidual`; off by default); own_first_conv (same conditions, independent of the other
     two) moves the normalisation and the 3 -> 32 first convolution with its BatchNorm and ReLU6 into the first-convolution
     kernels (`_OwnFirstConv`; the Sequential then holds the network alone, as with fuse_stem; off by default)."""
-    if head_fp32 and not fuse_bn_act:
-        raise ValueError("head_fp32 is a switch of the FusedResNet path (fuse_bn_act=True)")
+    key = canonical_name(name)
+    if head_fp32 not in (False, True, "inference"):
+        raise ValueError("head_fp32 must be False, True or 'inference'")
+    own_head = bool(head_fp32) and key == 'mobilenet_v2'
+    if head_fp32 and not fuse_bn_act and not own_head:
+        raise ValueError("head_fp32 is a switch of the FusedResNet path (fuse_bn_act=True) and of MobileNetV2")
+    if own_head and dtype != torch.bfloat16:
+        raise ValueError("head_fp32 needs a bfloat16 network (the head kernels work on bf16 activations)")
+    if own_head and not channels_last:
+        raise ValueError("head_fp32 needs channels_last=True (the head kernels work on channels_last storage)")
     if own_strided_conv and not fuse_bn_act:
         raise ValueError("own_strided_conv is a switch of the FusedResNet path (fuse_bn_act=True)")
-    key = canonical_name(name)
     for switch, on, kernels, layers in (('own_depthwise', own_depthwise, 'depthwise', 'the depthwise 3x3 layers'),
                                         ('own_pointwise', own_pointwise, 'pointwise', 'the 1x1 layers'),
                                         ('own_first_conv', own_first_conv, 'first-convolution', 'the first convolution')):
@@ -1186,6 +1243,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     if own_first_conv:                   # the module normalises: the Sequential holds the network alone
         use_own_first_conv_(net, mean, std)
         stem_fused = True
+    if own_head:                         # after the weights are loaded: the head keeps an fp32 copy of the Linear
+        use_own_head_(net, head_fp32)
     if fuse_bn_act and isinstance(net, ResNet):
         stem_fused = bool(fuse_stem)
         if stem_fused and dtype != torch.bfloat16:

@@ -51,7 +51,8 @@ extern "C" {
  * stores — ADIL_U8 as a source of adil_gather_images, adil_images_to_u8, adil_synth_store.  adil_pw_join_fwd /
  * adil_pw_join_bwd, and after them adil_conv3x3_s2_fwd / adil_conv3x3_s2_bwd, were added under 8: new symbols only, no
  * existing signature changed, and a library without them fails to load by name.  adil_dw3x3_fwd / adil_dw3x3_bwd joined them the
- * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those: both additive under 8. */
+ * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those, and
+ * adil_pool_head_fwd / adil_pool_head_bwd after those: all additive under 8. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -443,6 +444,34 @@ int adil_first3x3_fwd(const void* x, int x_dtype, const void* w_fwd, float mean0
                       int relu6, void* stream);
 int adil_first3x3_bwd(const void* g, const void* y, const float* scale, const void* w_bwd, float inv_std0, float inv_std1,
                       float inv_std2, void* gx, int gx_dtype, int B, int H, int W, int relu6, void* stream);
+
+/* Global average pooling + the last linear layer of the frozen classifier with fp32 logits, forward and input gradient, on
+ * the channels_last bf16 activation itself (the head of MobileNetV2: C = 1280, 7 x 7; the ResNet widths 512 and 2048 are
+ * covered too).  Only x and gx are bf16; weights, pooled features, logits and their gradients are fp32.
+ *     x, gx           [B][HW][C] bf16 : the channels_last storage of a (B, C, H, W) activation, HW = H W
+ *     w               [N][C] fp32     : the Linear's own layout (read by the backward, contiguous in c)
+ *     wt              [C][N] fp32     : its transpose (read by the forward, contiguous in n)
+ *     bias            [N] fp32
+ *     g, logits       [B][N] fp32
+ *     pooled, gpooled [B][C] fp32     : caller-provided OUTPUTS with defined values, not scratch
+ *   inv_hw = 1.0f / (float)HW, formed on the host.
+ *   adil_pool_head_fwd : S[b][c] = sum_hw x[b][hw][c] in fp32 (any order); pooled[b][c] = f32(S * inv_hw): ONE fp32 multiply;
+ *                        logits[b][n] = bias[n] + sum_c pooled[b][c] * w[n][c]: fp32 products and sums in any order, the
+ *                        bias at any position of the sum; the factors are the stored fp32 values themselves (no bf16
+ *                        rounding of pooled or w, no split).
+ *   adil_pool_head_bwd : gpooled[b][c] = sum_n g[b][n] * w[n][c] in fp32 (any order);
+ *                        gx[b][hw][c] = bf16( f32(gpooled[b][c] * inv_hw) ), nearest even, the same value for every hw.
+ *                        Every element of gx is written.  Input gradient only: the network is frozen.
+ * C % 8 == 0, 8 <= C <= 2048, 1 <= HW <= 65536, 1 <= B <= 65535 (the image index is a grid dimension), 1 <= N <= 65535:
+ * every N is correct, multiples of 4 take 16-byte loads and stores, the others element-wise ones.  x, gx, w, wt, g, logits,
+ * pooled, gpooled 16-byte aligned, bias 4-byte aligned.  A NULL pointer, a size outside these ranges or a misaligned
+ * pointer: ADIL_EINVAL before any launch, outputs untouched.  No load leaves the extents of an operand: the tails in B, C,
+ * HW and N are predicated, never clamped or over-read.  Element offsets are 64-bit (B HW C may pass 2^31).  Two launches
+ * per call on `stream` (a stream pass over x / gx and a small GEMM), no synchronisation, no allocation.  No atomics: bitwise
+ * reproducible. */
+int adil_pool_head_fwd(const void* x, const float* wt, const float* bias, float* pooled, float* logits, int B, int HW,
+                       int C, int N, void* stream);
+int adil_pool_head_bwd(const float* g, const float* w, float* gpooled, void* gx, int B, int HW, int C, int N, void* stream);
 
 #ifdef __cplusplus
 }

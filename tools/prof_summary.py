@@ -9,7 +9,7 @@ import sys
 
 OURS = ("synth", "grad_", "adamw", "pack_codes", "l1ball", "l2ball", "ista", "atom_", "gram", "rightmul", "image_metrics",
         "sum_partials", "fused", "zstep", "gather_images", "spd_inverse", "transpose_codes", "stem_", "maxpool_fwd",
-        "pw_conv", "conv3x3", "affine_act", "dw3x3", "pw8_", "first3x3_")
+        "pw_conv", "conv3x3", "affine_act", "dw3x3", "pw8_", "first3x3_", "head_")
 
 
 def short(name: str) -> str:
