@@ -1145,6 +1145,66 @@ def pw8_conv(x: Tensor, w2d: Tensor, wt2d: Tensor, scale: Tensor, shift: Tensor,
 
 
 # --------------------------------------------------------------------------- #
+def dense1x1_covers(x: Tensor, cin: int, cout: int) -> bool:
+    """What adil_dense1x1_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library): the limits
+    of adil_pw8_*."""
+    return pw8_conv_covers(x, cin, cout)
+
+
+class Dense1x1Function(torch.autograd.Function):
+    """eval-BatchNorm + ReLU + 1x1 convolution + eval-BatchNorm (+ ReLU) on channels_last bf16 tensors as one GEMM kernel
+    (adil_dense1x1_fwd); the input gradient takes the output ReLU's mask from the saved output and recomputes the input
+    ReLU's branch from the saved input (adil_dense1x1_bwd).  No weight gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, pscale, pshift, w2d, wt2d, scale, shift, relu):
+        lib = _lib.load()
+        b, k, h, w = x.shape
+        n = w2d.shape[0]
+        x2 = _nhwc(x)
+        y = torch.empty((b, h, w, n), dtype=torch.bfloat16, device=x.device)
+        _lib.check(lib.adil_dense1x1_fwd(_ptr(x2), _ptr(pscale), _ptr(pshift), _ptr(w2d), _ptr(scale), _ptr(shift), _ptr(y),
+                                         b * h * w, k, n, int(bool(relu)), _stream()), "adil_dense1x1_fwd")
+        ctx.save_for_backward(x2, y, pscale, pshift, wt2d, scale)
+        ctx.meta = (k, n, int(bool(relu)))
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x2, y, pscale, pshift, wt2d, scale = ctx.saved_tensors
+        k, n, relu = ctx.meta
+        gx = None
+        if ctx.needs_input_grad[0]:
+            g2 = _nhwc_grad(g)
+            b, h, w = g2.shape[0], g2.shape[1], g2.shape[2]
+            gx = torch.empty((b, h, w, k), dtype=torch.bfloat16, device=g2.device)
+            _lib.check(lib.adil_dense1x1_bwd(_ptr(g2), _ptr(y), _ptr(scale), _ptr(wt2d), _ptr(x2), _ptr(pscale), _ptr(pshift),
+                                             _ptr(gx), b * h * w, k, n, relu, _stream()), "adil_dense1x1_bwd")
+            gx = gx.permute(0, 3, 1, 2)
+        return gx, None, None, None, None, None, None, None
+
+
+def dense1x1_conv(x: Tensor, pscale: Tensor, pshift: Tensor, w2d: Tensor, wt2d: Tensor, scale: Tensor, shift: Tensor,
+                  relu: bool = False) -> Tensor:
+    """x (B,K,H,W) bf16 in channels_last memory format -> act((relu(x * pscale + pshift) . w2d^T) * scale + shift) as
+    (B,N,H,W), same format, no copies.  pscale / pshift (K,) fp32, w2d (N,K) and its transpose wt2d (K,N) bf16, scale /
+    shift (N,) fp32; act = ReLU with `relu`, else the identity."""
+    if w2d.dim() != 2:
+        raise ValueError(f"w2d must be a (N, K) matrix, got {tuple(w2d.shape)}")
+    n, k = w2d.shape
+    if not dense1x1_covers(x, k, n):
+        raise ValueError(f"adil_dense1x1 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with a {n} x {k} weight")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError("x must be in channels_last memory format (the kernels read it in place and the backward reads the "
+                         "saved x itself)")
+    _check_operands(x.device, ("pscale", pscale, (k,), torch.float32), ("pshift", pshift, (k,), torch.float32),
+                    ("w2d", w2d, (n, k), torch.bfloat16), ("wt2d", wt2d, (k, n), torch.bfloat16),
+                    ("scale", scale, (n,), torch.float32), ("shift", shift, (n,), torch.float32))
+    return Dense1x1Function.apply(x, pscale, pshift, w2d, wt2d, scale, shift, bool(relu))
+
+
+# --------------------------------------------------------------------------- #
 def pack_stem_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
     """(64,3,7,7) conv weight -> the two bf16 layouts of include/adil_hip.h: w_fwd [64][7][8][4], w_bwd [4][49][64]."""
     if tuple(weight.shape) != (64, 3, 7, 7):

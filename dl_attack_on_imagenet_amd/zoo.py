@@ -812,6 +812,100 @@ def use_own_pointwise_(net: nn.Module) -> int:
             + _rewrite_children_(net, _is_projection_block, _OwnInvertedResidual))
 
 
+class _Dense1x1Tables(_KeepsFp32):
+    """What `ops.dense1x1_conv` needs of a BatchNorm + ReLU + 1x1 convolution (+ BatchNorm + ReLU), as non-persistent
+    buffers (no state_dict entries): `pscale` / `pshift` [K] of the BatchNorm in front and `scale` / `shift` [N] of the one
+    behind (`_bn_affine`; ones and zeros where there is none); `wt2d` [K][N], the transposed weight, which is cast with
+    the network (its bf16 rounding is the weight's own).  The [N][K] weight is the convolution's own storage."""
+    _KEEP_FP32 = ('pscale', 'pshift', 'scale', 'shift')
+
+    def _init_tables(self, pre_bn, conv, bn):
+        self.cin, self.cout = conv.in_channels, conv.out_channels
+        pscale, pshift = _bn_affine(pre_bn)
+        if bn is not None:
+            scale, shift = _bn_affine(bn)
+        else:
+            scale, shift = torch.ones(self.cout, device=pscale.device), torch.zeros(self.cout, device=pscale.device)
+        for name, t in (('pscale', pscale), ('pshift', pshift), ('scale', scale), ('shift', shift),
+                        ('wt2d', conv.weight.detach().reshape(self.cout, self.cin).t().contiguous())):
+            self.register_buffer(name, t, persistent=False)
+
+    def _covers(self, x, conv):
+        return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and ops.dense1x1_covers(x, self.cin, self.cout)
+                and x.is_contiguous(memory_format=torch.channels_last) and conv.weight.dtype == torch.bfloat16
+                and self.wt2d.dtype == torch.bfloat16 and self.wt2d.device == x.device and self.scale.device == x.device
+                and self.pscale.device == x.device)
+
+    def _dense1x1(self, x, conv, relu):
+        w2d = conv.weight.reshape(self.cout, self.cin)
+        if not w2d.is_contiguous():
+            w2d = w2d.contiguous()
+        return ops.dense1x1_conv(x, self.pscale, self.pshift, w2d, self.wt2d, self.scale, self.shift, relu)
+
+
+def _is_dense1x1(pre_bn, conv, bn) -> bool:
+    return (isinstance(pre_bn, nn.BatchNorm2d) and _plain_conv(conv, 1, (1,), 1) and (bn is None or isinstance(bn, nn.BatchNorm2d))
+            and pre_bn.num_features == conv.in_channels and conv.in_channels in ops.PW8_CHANNELS
+            and conv.out_channels in ops.PW8_CHANNELS)
+
+
+def _is_dense_layer(m) -> bool:
+    return (isinstance(m, _DenseLayer) and isinstance(m.relu1, nn.ReLU) and isinstance(m.relu2, nn.ReLU)
+            and _is_dense1x1(m.norm1, m.conv1, m.norm2))
+
+
+def _is_transition(m) -> bool:
+    return (type(m) is nn.Sequential and list(m._modules) == ['norm', 'relu', 'conv', 'pool'] and isinstance(m.relu, nn.ReLU)
+            and _is_dense1x1(m.norm, m.conv, None))
+
+
+class _OwnDenseLayer(_Dense1x1Tables):
+    """A `_DenseLayer` whose norm1 -> relu1 -> conv1 -> norm2 -> relu2 on the concatenated input is ONE `ops.dense1x1_conv`
+    call where the kernel covers the input; conv2 (3x3) runs as it is.  The submodules keep their names (same state_dict
+    keys) and serve every other input: CPU, fp32, not channels_last, tables on another device."""
+
+    def __init__(self, layer: _DenseLayer):
+        super().__init__()
+        if not _is_dense_layer(layer):
+            raise ValueError("not a BatchNorm + ReLU + 1x1 conv + BatchNorm + ReLU + 3x3 conv dense layer")
+        for name in ('norm1', 'relu1', 'conv1', 'norm2', 'relu2', 'conv2'):
+            self.add_module(name, getattr(layer, name))
+        self._init_tables(self.norm1, self.conv1, self.norm2)
+
+    def forward(self, feats):
+        x = torch.cat(feats, 1)
+        if self._covers(x, self.conv1):
+            return self.conv2(self._dense1x1(x, self.conv1, True))
+        x = self.conv1(self.relu1(self.norm1(x)))
+        return self.conv2(self.relu2(self.norm2(x)))
+
+
+class _OwnTransition(_Dense1x1Tables):
+    """A DenseNet transition (`norm -> relu -> conv 1x1 -> pool`) whose first three layers are ONE `ops.dense1x1_conv`
+    call with the identity behind the convolution (scale 1, shift 0).  The submodules keep their names (same state_dict
+    keys) and serve every input the kernel does not cover."""
+
+    def __init__(self, block: nn.Sequential):
+        super().__init__()
+        if not _is_transition(block):
+            raise ValueError("not a BatchNorm + ReLU + 1x1 conv + pool transition")
+        for name in ('norm', 'relu', 'conv', 'pool'):
+            self.add_module(name, getattr(block, name))
+        self._init_tables(self.norm, self.conv, None)
+
+    def forward(self, x):
+        if self._covers(x, self.conv):
+            return self.pool(self._dense1x1(x, self.conv, False))
+        return self.pool(self.conv(self.relu(self.norm(x))))
+
+
+def use_own_dense_pointwise_(net: nn.Module) -> int:
+    """Replace every `_DenseLayer` of the network by an `_OwnDenseLayer` and every transition by an `_OwnTransition`;
+    returns how many 1x1 layers were rewritten (DenseNet-121: 58 dense layers and 3 transitions)."""
+    return (_rewrite_children_(net, _is_dense_layer, _OwnDenseLayer)
+            + _rewrite_children_(net, _is_transition, _OwnTransition))
+
+
 def _is_first_conv_block(block) -> bool:
     if not isinstance(block, _ConvBNReLU6) or len(block) != 3:
         return False
@@ -1190,7 +1284,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      fold_bn: bool = False, pad_input_channels: int = 0, fuse_bn_act: bool = False,
                      fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False,
                      own_depthwise: bool = False, own_pointwise: bool = False,
-                     own_first_conv: bool = False) -> nn.Module:
+                     own_first_conv: bool = False, own_dense_pointwise: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
@@ -1205,7 +1299,10 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     own_depthwise) runs the 34 1x1 layers with their BatchNorm, ReLU6 and residual add in the narrow-channel GEMM kernel
     (`_OwnPointwise` / `_OwnInvertedResidual`; off by default); own_first_conv (same conditions, independent of the other
     two) moves the normalisation and the 3 -> 32 first convolution with its BatchNorm and ReLU6 into the first-convolution
-    kernels (`_OwnFirstConv`; the Sequential then holds the network alone, as with fuse_stem; off by default)."""
+    kernels (`_OwnFirstConv`; the Sequential then holds the network alone, as with fuse_stem; off by default);
+    own_dense_pointwise (DenseNet-121, bf16, channels_last) runs the 61 pre-activated 1x1 layers (58 dense layers, 3
+    transitions) with the BatchNorm + ReLU in front and behind in the pre-activated pointwise kernels (`_OwnDenseLayer` /
+    `_OwnTransition`; off by default)."""
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
@@ -1227,6 +1324,15 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
             raise ValueError(f"{switch} needs a bfloat16 network (the {kernels} kernels work on bf16 activations)")
         if on and not channels_last:
             raise ValueError(f"{switch} needs channels_last=True (the {kernels} kernels work on channels_last storage)")
+    if own_dense_pointwise and key != 'densenet121':
+        raise ValueError("own_dense_pointwise is a switch of DenseNet-121 (no other network has the pre-activated 1x1 layers "
+                         "rewritten)")
+    if own_dense_pointwise and dtype != torch.bfloat16:
+        raise ValueError("own_dense_pointwise needs a bfloat16 network (the pre-activated pointwise kernels work on bf16 "
+                         "activations)")
+    if own_dense_pointwise and not channels_last:
+        raise ValueError("own_dense_pointwise needs channels_last=True (the pre-activated pointwise kernels work on "
+                         "channels_last storage)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1243,6 +1349,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     if own_first_conv:                   # the module normalises: the Sequential holds the network alone
         use_own_first_conv_(net, mean, std)
         stem_fused = True
+    if own_dense_pointwise:              # after the weights are loaded: the tables are derived from them
+        use_own_dense_pointwise_(net)
     if own_head:                         # after the weights are loaded: the head keeps an fp32 copy of the Linear
         use_own_head_(net, head_fp32)
     if fuse_bn_act and isinstance(net, ResNet):

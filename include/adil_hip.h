@@ -52,7 +52,8 @@ extern "C" {
  * adil_pw_join_bwd, and after them adil_conv3x3_s2_fwd / adil_conv3x3_s2_bwd, were added under 8: new symbols only, no
  * existing signature changed, and a library without them fails to load by name.  adil_dw3x3_fwd / adil_dw3x3_bwd joined them the
  * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those, and
- * adil_pool_head_fwd / adil_pool_head_bwd after those: all additive under 8. */
+ * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those: all additive
+ * under 8. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -472,6 +473,38 @@ int adil_first3x3_bwd(const void* g, const void* y, const float* scale, const vo
 int adil_pool_head_fwd(const void* x, const float* wt, const float* bias, float* pooled, float* logits, int B, int HW,
                        int C, int N, void* stream);
 int adil_pool_head_bwd(const float* g, const float* w, float* gpooled, void* gx, int B, int HW, int C, int N, void* stream);
+
+/* Pre-activated pointwise (1x1, stride 1) convolution of the frozen DenseNet-121: the eval-BatchNorm + ReLU IN FRONT of the
+ * convolution (on the concatenated input of a dense layer or a transition, K = 64 .. 1024 in steps of 32) is applied on the
+ * way into the GEMM, the eval-BatchNorm + ReLU behind it on the accumulators; forward and input gradient, one kernel each
+ * way.  channels_last bf16 storage, M = B H W pixels:
+ *     x, xin, gx     [M][K] bf16
+ *     w              [N][K] bf16, wt [K][N] bf16 its transpose
+ *     pscale, pshift [K] fp32 : the BatchNorm in front (scale = gamma / sqrt(var + eps), shift = beta - mean * scale)
+ *     scale, shift   [N] fp32 : the BatchNorm behind
+ *     y, g           [M][N] bf16
+ *   Prologue : pre[m][k] = fadd_rn(fmul_rn(f32(x[m][k]), pscale[k]), pshift[k]): the product and the sum are each rounded
+ *              to fp32, no contraction, so an fp32 restatement reproduces the branch and the bits;
+ *              a = bf16_rne(max(pre, 0)); every pre <= 0 gives +0.
+ *   adil_dense1x1_fwd : acc = sum_k a[m][k] * w[n][k], bf16 MFMA with fp32 accumulation in any order;
+ *                       y = bf16_rne(act(acc * scale[n] + shift[n])); act 1 = ReLU, NOT ReLU6: max(., 0), non-positive
+ *                       values written as +0; act 0 = the identity (a transition calls it with scale = 1, shift = 0; there
+ *                       is no NULL special case).
+ *   adil_dense1x1_bwd : gz = bf16_rne(g * scale[n]): one fp32 product, one rounding; with act 1, gz is masked by [y > 0],
+ *                       taken from the stored bf16 y by comparing VALUES (-0.0 is a zero; there is no precondition);
+ *                       t = sum_n gz[m][n] * wt[k][n] in fp32; gx[m][k] = bf16_rne(t * pscale[k]) where pre[m][k] > 0,
+ *                       else +0; pre is recomputed from xin by the forward's two operations, so the mask is the forward's
+ *                       branch.  Every element of gx is written.  Input gradient only: the network is frozen.  With act 0,
+ *                       y may be NULL.
+ * Limits as adil_pw8_*: K % 8 == 0, N % 8 == 0, 8 <= K, N <= 2048, any M >= 1, 16-byte aligned bf16 pointers, 4-byte aligned
+ * tables.  A NULL mandatory pointer, act outside {0, 1}, a size outside the limits or a misaligned pointer: ADIL_EINVAL
+ * before any launch, outputs untouched.  No load or store leaves an operand's extent, the [K] / [N] tables included: tails
+ * in M, K and N are clipped and zero-filled on BOTH MFMA operands.  Element offsets are 64-bit.  One launch per call on
+ * `stream`, no allocation, no synchronisation.  No atomics: bitwise reproducible. */
+int adil_dense1x1_fwd(const void* x, const float* pscale, const float* pshift, const void* w, const float* scale,
+                      const float* shift, void* y, int M, int K, int N, int act, void* stream);
+int adil_dense1x1_bwd(const void* g, const void* y, const float* scale, const void* wt, const void* xin, const float* pscale,
+                      const float* pshift, void* gx, int M, int K, int N, int act, void* stream);
 
 #ifdef __cplusplus
 }

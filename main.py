@@ -30,6 +30,9 @@ def build_parser():
     p.add_argument('--figure', default='attack_samples.png')
     p.add_argument('--graph', type=int, default=1,
                    help='replay the inference iterations from a hipGraph (a one-image attack is launch-bound); 0 = eager')
+    p.add_argument('--own-dense-pointwise', type=int, default=0, choices=[0, 1],
+                   help='-m densenet: 1 = a bfloat16 channels_last network whose 61 pre-activated 1x1 layers run in the '
+                        'pre-activated pointwise kernels; 0 (default) = the fp32 library network.  Ignored otherwise')
     return p
 
 
@@ -40,13 +43,20 @@ def main(args):
     torch.cuda.set_device(0)
     device = torch.device('cuda', 0)
     model_name = args.model.lower()          # names the dictionary file, as upstream (main.py:40, adil.py:89-91)
-    model = zoo.build_classifier(model_name, weights=args.weights, device=device)
+    own_dense = bool(args.own_dense_pointwise) and zoo.canonical_name(model_name) == 'densenet121'
+    if own_dense:                            # the kernels work on bf16 channels_last activations
+        net = zoo.build_classifier(model_name, weights=args.weights, device=device, dtype=torch.bfloat16,
+                                   channels_last=True, own_dense_pointwise=True)
+        model = lambda x: net(x.to(torch.bfloat16)).float()
+    else:
+        net = model = zoo.build_classifier(model_name, weights=args.weights, device=device)
     if args.synthetic:
         im = torch.rand(3, args.image_size, args.image_size, generator=torch.Generator().manual_seed(0))
     else:
         im = load_image(args.image)
     eps = 8 / 255
-    attack = ADIL(model, eps=eps, model_name=model_name, use_graph=bool(args.graph))     # main.py:80
+    attack = ADIL(net, eps=eps, model_name=model_name, use_graph=bool(args.graph),     # main.py:80
+                  stream_dtype=torch.bfloat16 if own_dense else None)
     im = im.to(device)
     label = model(im.unsqueeze(0)).argmax(dim=-1)
     adversary = attack(im.unsqueeze(0), label)
