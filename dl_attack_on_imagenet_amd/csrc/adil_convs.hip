@@ -2,7 +2,8 @@
 //   pw_conv_fwd / pw_conv_bwd   1x1 convolutions (stride 1, and the stride-2 downsample ones through an in-kernel
 //                               gather) as GEMMs with the BatchNorm / residual / ReLU epilogue (and
 //                               the previous layer's BatchNorm + ReLU as a prologue) applied on chip, forward and input
-//                               gradient
+//                               gradient (the gradient at 64 / 128 output channels per workgroup, or at 256 / 512
+//                               in an 8-wave form that prepares its operand once: a measured table picks the tile)
 //   pw_join                     conv3 of a bottleneck and conv1 of the next one as one kernel, forward and input
 //                               gradient (the C-channel tensor between them stays on chip)
 //   conv3x3                    3x3 / stride-1 convolutions as an implicit GEMM with linear pixel tiling
@@ -193,20 +194,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRO && BN =
 // The epilogue backward is applied to the X-operand chunk on its way from registers to LDS (it would otherwise be a
 // separate kernel writing and re-reading an M x N tensor), and g2 lets the caller hand over the two gradients that
 // meet at a residual join without adding them first (autograd's add kernels were 3 ms of a 46 ms step).
-template <int BO, bool G3>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 || G3) ? 2 : 3))) void pw_conv_bwd_kernel(
+//   NW = 4 waves: each owns 32 pixels x BO channels (BO = 64, 128), one LDS buffer, two workgroups per CU.
+//   NW = 8 (the wide tiles, BO = 256 and 512, G3 = false only): 4 pixel groups x 2 channel halves, so the operand chunk —
+//   three M x N loads, the add, mask, scale and rounding of store_tiles — is prepared once for 256 or 512 output
+//   channels instead of once per 128 (at K = 512, N = 2048 a narrow workgroup pulls 1.5 MB of operand through L2 for 67
+//   MFLOP).  ONE workgroup of 8 waves lives on a CU (166 / 252 registers; BO = 256 with 4 waves and 128 accumulators, or
+//   with 8 waves under a 128-register budget, spills).  BO = 256 double-buffers the tiles in the LDS it has to itself
+//   (2 x 54 KB): one barrier per chunk, and the waves that are ahead prepare chunk i+1 while the others still multiply
+//   chunk i.  BO = 512 (90 KB of tiles, 130 KB for the output transpose) keeps the single buffer.
+//   Each output element sees the same MFMA sequence at every tile: the results are bitwise the same.
+template <int BO, bool G3, int NW>
+__global__ __launch_bounds__(NW * 64) __attribute__((amdgpu_waves_per_eu((NW == 8 || BO == 128 || G3) ? 2 : 3))) void pw_conv_bwd_kernel(
     const bf16_t* __restrict__ g, const bf16_t* __restrict__ g2, const bf16_t* __restrict__ y,
     const float* __restrict__ scale, const bf16_t* __restrict__ wt, bf16_t* __restrict__ gx, bf16_t* __restrict__ gres,
     int M, int K, int N, int relu, int MT, int OT, const bf16_t* __restrict__ xin, const float* __restrict__ pscale,
     const float* __restrict__ pshift, const bf16_t* __restrict__ g3, int sub_w, int sub_hw) {
-    constexpr int CT = BO / 32;
-    constexpr int XCH = PW_BM * PW_BK / 8 / 256;         // 4
-    constexpr int WCH = BO * PW_BK / 8 / 256;
+    constexpr int NT = NW * 64;                          // threads
+    constexpr int BW = BO / (NW / 4);                    // output channels per wave
+    constexpr int CT = BW / 32;
+    constexpr int XCH = PW_BM * PW_BK / 8 / NT;          // 4 (2 with 8 waves)
+    constexpr int WCH = BO * PW_BK / 8 / NT;
     constexpr int OS = BO + 8;
+    constexpr bool DB = NW == 8 && BO == 256;            // two tile buffers (BO = 512: 2 x 90 KB do not fit)
+    constexpr int BUFE = (PW_BM + BO) * PW_LS;           // elements of one buffer
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16_t* sx = reinterpret_cast<bf16_t*>(smem_raw);    // [128][PW_LS]  gz chunk
     bf16_t* sw = sx + PW_BM * PW_LS;                     // [BO][PW_LS]   wt chunk
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
+    const int tid = threadIdx.x, lane = tid & 63, w = (tid >> 6) & 3, wc = tid >> 8, c = lane & 31, h = lane >> 5;
     int mt, ot;
     if ((MT & 7) == 0) {
         const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
@@ -222,15 +236,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 
     __shared__ __attribute__((aligned(16))) float ssc[2048];     // BatchNorm scale of every reduction channel
     {   // N <= 2048 floats = at most two float4 per thread, both in flight together (a rolled scalar loop pays up to
         // eight memory round trips before the first tile load is even issued)
-        float4 sv[2];
+        float4 sv[512 / NT];
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int i4 = tid + 256 * j;
+        for (int j = 0; j < 512 / NT; ++j) {
+            const int i4 = tid + NT * j;
             sv[j] = *reinterpret_cast<const float4*>(scale + (4 * i4 < N ? 4 * i4 : 0));
         }
 #pragma unroll
-        for (int j = 0; j < 2; ++j) {
-            const int i4 = tid + 256 * j;
+        for (int j = 0; j < 512 / NT; ++j) {
+            const int i4 = tid + NT * j;
             if (4 * i4 < N) *reinterpret_cast<float4*>(ssc + 4 * i4) = sv[j];
         }
     }
@@ -244,7 +258,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 
     if (G3) {
 #pragma unroll
         for (int i = 0; i < XCH; ++i) {
-            const int id = tid + 256 * i, row = id >> 3;
+            const int id = tid + NT * i, row = id >> 3;
             const int mm = (m0 + row < M) ? m0 + row : M - 1;
             const int hw4 = 4 * sub_hw, w2 = 2 * sub_w;
             const int n = mm / hw4, r = mm - n * hw4, hh = r / w2, ww = r - hh * w2;
@@ -256,7 +270,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 
     auto load_tiles = [&](int nc) {
 #pragma unroll
         for (int i = 0; i < XCH; ++i) {
-            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
+            const int id = tid + NT * i, row = id >> 3, ch = id & 7;
             const int mm = m0 + row;
             const size_t at = (size_t)(mm < M ? mm : M - 1) * N + nc * PW_BK + ch * 8;
             gr[i] = *reinterpret_cast<const u32x4*>(g + at);
@@ -266,14 +280,14 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 
         }
 #pragma unroll
         for (int i = 0; i < WCH; ++i) {
-            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
+            const int id = tid + NT * i, row = id >> 3, ch = id & 7;
             wr[i] = *reinterpret_cast<const u32x4*>(wt + (size_t)(k0 + row) * N + nc * PW_BK + ch * 8);
         }
     };
-    auto store_tiles = [&](int nc) {
+    auto store_tiles = [&](int nc, int buf) {
 #pragma unroll
         for (int i = 0; i < XCH; ++i) {
-            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
+            const int id = tid + NT * i, row = id >> 3, ch = id & 7;
             const f32x2* s2 = reinterpret_cast<const f32x2*>(ssc + nc * PW_BK + ch * 8);
             u32x4 rs, gz;                                             // gres chunk, gz chunk (packed bf16)
 #pragma unroll
@@ -287,12 +301,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 
             }
             const int mm = m0 + row;
             if (write_res && mm < M) *reinterpret_cast<u32x4*>(gres + (size_t)mm * N + nc * PW_BK + ch * 8) = rs;
-            *reinterpret_cast<u32x4*>(sx + row * PW_LS + ch * 8) = gz;
+            *reinterpret_cast<u32x4*>(sx + buf * BUFE + row * PW_LS + ch * 8) = gz;
         }
 #pragma unroll
         for (int i = 0; i < WCH; ++i) {
-            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
-            *reinterpret_cast<u32x4*>(sw + row * PW_LS + ch * 8) = wr[i];
+            const int id = tid + NT * i, row = id >> 3, ch = id & 7;
+            *reinterpret_cast<u32x4*>(sw + buf * BUFE + row * PW_LS + ch * 8) = wr[i];
         }
     };
 
@@ -302,21 +316,33 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[ct][r] = 0.0f;
-    for (int it = 0; it < nn; ++it) {
-        store_tiles(it);
-        if (it + 1 < nn) load_tiles(it + 1);
+    if (DB) {                                            // chunk 0 into buffer 0; from then on chunk it + 1 is written
+        store_tiles(0, 0);                               // into the other buffer after the MFMAs of chunk it
+        if (1 < nn) load_tiles(1);
         lds_barrier();
-        const bf16_t* bx = sx + (w * 32 + c) * PW_LS + 8 * h;
-        const bf16_t* bw = sw + c * PW_LS + 8 * h;
+    }
+    for (int it = 0; it < nn; ++it) {
+        if (!DB) {
+            store_tiles(it, 0);
+            if (it + 1 < nn) load_tiles(it + 1);
+            lds_barrier();
+        }
+        const int cur = DB ? (it & 1) : 0;
+        const bf16_t* bx = sx + cur * BUFE + (w * 32 + c) * PW_LS + 8 * h;
+        const bf16_t* bw = sw + cur * BUFE + (wc * BW + c) * PW_LS + 8 * h;
 #pragma unroll
         for (int ks = 0; ks < PW_BK / 16; ++ks) {
             const bf16x8 b = lds8(bx + 16 * ks);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) mma16(acc[ct], lds8(bw + ct * 32 * PW_LS + 16 * ks), b);
         }
+        if (DB && it + 1 < nn) {                         // nobody reads buffer cur ^ 1 in this iteration
+            store_tiles(it + 1, cur ^ 1);
+            if (it + 2 < nn) load_tiles(it + 2);
+        }
         lds_barrier();
     }
-    bf16_t* so = reinterpret_cast<bf16_t*>(smem_raw) + w * 32 * OS;
+    bf16_t* so = reinterpret_cast<bf16_t*>(smem_raw) + w * 32 * OS + wc * BW;   // this wave's 32 px x BW corner
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
 #pragma unroll
@@ -329,7 +355,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 
     }
     // optional epilogue: the forward fed this layer relu(xin * pscale + pshift) computed on the fly (xin = raw output
     // of the previous convolution), so the gradient handed back is wrt xin:  gx * [xin*pscale+pshift > 0] * pscale
-    constexpr int CPP = BO / 8;
+    constexpr int CPP = BW / 8;
+    const int kw0 = k0 + wc * BW;                        // first output channel of this wave
 #pragma unroll
     for (int i = 0; i < 32 * CPP / 64; ++i) {
         const int id = lane + 64 * i, px = id / CPP, ch = id - px * CPP;
@@ -339,31 +366,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu((BO == 128 
             if (xin != nullptr) {
                 float v[8], xv[8];
                 unpack8(t, v);
-                unpack8(*reinterpret_cast<const u32x4*>(xin + (size_t)mm * K + k0 + ch * 8), xv);
-                const float4 a0 = *reinterpret_cast<const float4*>(pscale + k0 + ch * 8);
-                const float4 a1 = *reinterpret_cast<const float4*>(pscale + k0 + ch * 8 + 4);
-                const float4 b0 = *reinterpret_cast<const float4*>(pshift + k0 + ch * 8);
-                const float4 b1 = *reinterpret_cast<const float4*>(pshift + k0 + ch * 8 + 4);
+                unpack8(*reinterpret_cast<const u32x4*>(xin + (size_t)mm * K + kw0 + ch * 8), xv);
+                const float4 a0 = *reinterpret_cast<const float4*>(pscale + kw0 + ch * 8);
+                const float4 a1 = *reinterpret_cast<const float4*>(pscale + kw0 + ch * 8 + 4);
+                const float4 b0 = *reinterpret_cast<const float4*>(pshift + kw0 + ch * 8);
+                const float4 b1 = *reinterpret_cast<const float4*>(pshift + kw0 + ch * 8 + 4);
                 const float ps[8] = {a0.x, a0.y, a0.z, a0.w, a1.x, a1.y, a1.z, a1.w};
                 const float pb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
 #pragma unroll
                 for (int j = 0; j < 8; ++j) v[j] = (xv[j] * ps[j] + pb[j] > 0.0f) ? v[j] * ps[j] : 0.0f;
                 t = pack8(v);
             }
-            *reinterpret_cast<u32x4*>(gx + (size_t)mm * K + k0 + ch * 8) = t;
+            *reinterpret_cast<u32x4*>(gx + (size_t)mm * K + kw0 + ch * 8) = t;
         }
     }
 }
 
-template <int BO, bool G3>
+template <int BO, bool G3, int NW = 4>
 int launch_pw_bwd(const void* g, const void* g2, const void* y, const float* scale, const void* wt, void* gx, void* gres,
                   int M, int K, int N, int relu, const void* xin, const float* pscale, const float* pshift, const void* g3,
                   int sub_w, int sub_hw, hipStream_t st) {
     const int MT = (M + PW_BM - 1) / PW_BM, OT = K / BO;
-    const size_t tiles = (size_t)(PW_BM + BO) * PW_LS * sizeof(bf16_t);
+    const size_t tiles = (size_t)(NW == 8 && BO == 256 ? 2 : 1) * (PW_BM + BO) * PW_LS * sizeof(bf16_t);
     const size_t outb = (size_t)4 * 32 * (BO + 8) * sizeof(bf16_t);
     const size_t lds = tiles > outb ? tiles : outb;
-    hipLaunchKernelGGL((pw_conv_bwd_kernel<BO, G3>), dim3((unsigned)(MT * OT)), dim3(256), lds, st, (const bf16_t*)g,
+    if (lds > 48 * 1024) {                               // BO = 256: 108 KB, BO = 512: 130 KB, one workgroup per CU
+        const hipError_t e = hipFuncSetAttribute((const void*)pw_conv_bwd_kernel<BO, G3, NW>,
+                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        if (e != hipSuccess) return (int)e;
+    }
+    hipLaunchKernelGGL((pw_conv_bwd_kernel<BO, G3, NW>), dim3((unsigned)(MT * OT)), dim3(NW * 64), lds, st, (const bf16_t*)g,
                        (const bf16_t*)g2, (const bf16_t*)y, scale, (const bf16_t*)wt, (bf16_t*)gx, (bf16_t*)gres, M, K, N,
                        relu, MT, OT, (const bf16_t*)xin, pscale, pshift, (const bf16_t*)g3, sub_w, sub_hw);
     ADIL_CHECK_LAUNCH();
@@ -399,23 +431,99 @@ int launch_pw_fwd(const void* x, const void* w, const float* scale, const float*
 
 }  // namespace
 
-extern "C" int adil_pw_conv_bwd(const void* g, const void* g2, const void* y, const float* scale, const void* wt, void* gx,
-                                void* gres, int M, int K, int N, int relu, const void* xin, const float* pscale,
-                                const float* pshift, const void* g3, int sub_w, int sub_hw, void* stream) {
-    ADIL_ENTER();
+// Which output-channel tile BO a G3 = false call runs at.  Every tile gives the same bits (same MFMA sequence, same
+// rounding points: only the split of pixels and output channels over workgroups differs), so this is a matter of speed
+// alone.  0 = the table below, 1 = the narrow tiles (128, or 64 where K % 128) everywhere, 2 = the widest tile that
+// divides K (512, 256) wherever one does.
+static int g_pw_route_policy = 0;
+
+// The table: (K, N), a range of M and the tile that won there.  A row is in it only where that tile's median beat the
+// narrow tile's median by more than the narrow tile's own max - min over five alternating rounds, and it names the
+// faster of the two wide tiles (tools/bench_pw_wide.py --only kernels at --batch 512, 256, 128 and 64:
+// profiles/pw_wide_bench.json and pw_wide_bench_b{256,128,64}.json).  The bounds are the measured pixel counts
+// (B x 28 x 28, B x 14 x 14, B x 7 x 7 at those batches), open above where the largest batch passed.  Next to the bytes,
+// what decides is the round fit: a wide tile runs one workgroup per CU (256 slots), the narrow one two (512 slots) with
+// 2 or 4 times the workgroups.  So the stage-3 conv3 gradient (K = 256) wins at 196 and 392 wide workgroups and loses at
+// 784 (3.06 rounds pay for 4), and 512 loses to 256 once it leaves most CUs without a workgroup.  K = 256 with
+// N <= 128 (stages 1 and 2, at the HBM limit already) never passed.
+struct PwWideRow { int K, N, m_lo, m_hi, bo; };
+static const PwWideRow kPwWide[] = {
+    {512, 128, 200704, INT32_MAX, 512},    // layer2 conv1:        167 -> 152 us at B = 512; slower at B = 128
+    {512, 256, 50176, INT32_MAX, 512},     // layer3.0 conv1:      280 -> 230 us at B = 512
+    {256, 1024, 25088, 50176, 256},        // layer3 conv3:         65 -> 43 us at B = 128, 117 -> 106 at 256; 203 -> 208 at 512
+    {1024, 256, 12544, INT32_MAX, 512},    // layer3 conv1:        139 -> 114 us at B = 512
+    {1024, 512, 12544, INT32_MAX, 512},    // layer4.0 conv1:      236 -> 185 us at B = 512
+    {512, 2048, 25088, INT32_MAX, 512},    // layer4 conv3:        257 -> 133 us at B = 512 (256: 151)
+    {512, 2048, 12544, 25087, 256},        //                      123 -> 71 us at B = 256 (512: 89)
+    {2048, 512, 6272, INT32_MAX, 512},     // layer4 conv1:        114 -> 97 us at B = 512
+    {2048, 512, 3136, 6271, 256},
+    {512, 1024, 25088, INT32_MAX, 512},    // layer3.0 downsample: 199 -> 173 us at B = 512
+    {512, 1024, 12544, 25087, 256},
+    {1024, 2048, 12544, INT32_MAX, 512},   // layer4.0 downsample: 203 -> 145 us at B = 512
+    {1024, 2048, 3136, 12543, 256},
+};
+
+static int pw_bwd_tile(int M, int K, int N) {
+    const int narrow = (K % 128 == 0) ? 128 : 64;
+    if (K % 256 || g_pw_route_policy == 1) return narrow;
+    if (g_pw_route_policy == 2) return (K % 512 == 0) ? 512 : 256;
+    for (const PwWideRow& r : kPwWide)
+        if (r.K == K && r.N == N && M >= r.m_lo && M <= r.m_hi) return r.bo;
+    return narrow;
+}
+
+static int pw_bwd_check(const void* g, const void* y, const float* scale, const void* wt, void* gx, int M, int K, int N,
+                        int relu, const void* xin, const float* pscale, const float* pshift, const void* g3, int sub_w,
+                        int sub_hw) {
     if (!g || !scale || !wt || !gx || (relu && !y) || M <= 0 || K <= 0 || N <= 0 || (N % PW_BK) || (K % 64) || N > 2048)
         return ADIL_EINVAL;
     if (xin && (!pscale || !pshift)) return ADIL_EINVAL;
     if (g3 && (sub_w <= 0 || sub_hw <= 0 || sub_hw % sub_w || M % (4 * sub_hw))) return ADIL_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
+    return 0;
+}
+
+static int pw_bwd_run(int bo, const void* g, const void* g2, const void* y, const float* scale, const void* wt, void* gx,
+                      void* gres, int M, int K, int N, int relu, const void* xin, const float* pscale, const float* pshift,
+                      const void* g3, int sub_w, int sub_hw, hipStream_t st) {
     if (g3) {
-        if (K % 128 == 0)
+        if (bo == 128)
             return launch_pw_bwd<128, true>(g, g2, y, scale, wt, gx, gres, M, K, N, relu, xin, pscale, pshift, g3, sub_w, sub_hw, st);
         return launch_pw_bwd<64, true>(g, g2, y, scale, wt, gx, gres, M, K, N, relu, xin, pscale, pshift, g3, sub_w, sub_hw, st);
     }
-    if (K % 128 == 0)
+    if (bo == 512)
+        return launch_pw_bwd<512, false, 8>(g, g2, y, scale, wt, gx, gres, M, K, N, relu, xin, pscale, pshift, nullptr, 0, 0, st);
+    if (bo == 256)
+        return launch_pw_bwd<256, false, 8>(g, g2, y, scale, wt, gx, gres, M, K, N, relu, xin, pscale, pshift, nullptr, 0, 0, st);
+    if (bo == 128)
         return launch_pw_bwd<128, false>(g, g2, y, scale, wt, gx, gres, M, K, N, relu, xin, pscale, pshift, nullptr, 0, 0, st);
     return launch_pw_bwd<64, false>(g, g2, y, scale, wt, gx, gres, M, K, N, relu, xin, pscale, pshift, nullptr, 0, 0, st);
+}
+
+extern "C" int adil_pw_conv_bwd(const void* g, const void* g2, const void* y, const float* scale, const void* wt, void* gx,
+                                void* gres, int M, int K, int N, int relu, const void* xin, const float* pscale,
+                                const float* pshift, const void* g3, int sub_w, int sub_hw, void* stream) {
+    ADIL_ENTER();
+    const int rc = pw_bwd_check(g, y, scale, wt, gx, M, K, N, relu, xin, pscale, pshift, g3, sub_w, sub_hw);
+    if (rc) return rc;
+    const int bo = g3 ? ((K % 128 == 0) ? 128 : 64) : pw_bwd_tile(M, K, N);
+    return pw_bwd_run(bo, g, g2, y, scale, wt, gx, gres, M, K, N, relu, xin, pscale, pshift, g3, sub_w, sub_hw, (hipStream_t)stream);
+}
+
+extern "C" int adil_pw_conv_bwd_tile(const void* g, const void* g2, const void* y, const float* scale, const void* wt,
+                                     void* gx, void* gres, int M, int K, int N, int relu, const void* xin,
+                                     const float* pscale, const float* pshift, const void* g3, int sub_w, int sub_hw,
+                                     void* stream, int bo) {
+    ADIL_ENTER();
+    const int rc = pw_bwd_check(g, y, scale, wt, gx, M, K, N, relu, xin, pscale, pshift, g3, sub_w, sub_hw);
+    if (rc) return rc;
+    if ((bo != 64 && bo != 128 && bo != 256 && bo != 512) || K % bo || (bo >= 256 && g3)) return ADIL_EINVAL;
+    return pw_bwd_run(bo, g, g2, y, scale, wt, gx, gres, M, K, N, relu, xin, pscale, pshift, g3, sub_w, sub_hw, (hipStream_t)stream);
+}
+
+extern "C" int adil_pw_route_policy(int policy) {
+    const int prev = g_pw_route_policy;
+    if (policy >= 0 && policy <= 2) g_pw_route_policy = policy;
+    return prev;
 }
 
 extern "C" int adil_pw_conv_fwd(const void* x, const void* w, const float* scale, const float* shift, const void* res,

@@ -53,7 +53,7 @@ extern "C" {
  * existing signature changed, and a library without them fails to load by name.  adil_dw3x3_fwd / adil_dw3x3_bwd joined them the
  * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those, and
  * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those: all additive
- * under 8. */
+ * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls neither). */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -330,6 +330,17 @@ int adil_pw_conv_fwd(const void* x, const void* w, const float* scale, const flo
 int adil_pw_conv_bwd(const void* g, const void* g2, const void* y, const float* scale, const void* wt, void* gx, void* gres,
                      int M, int K, int N, int relu, const void* xin, const float* pscale, const float* pshift, const void* g3,
                      int sub_w, int sub_hw, void* stream);
+/* adil_pw_conv_bwd picks the output-channel tile of its workgroups (64, 128, or the wide 256 / 512 of the 8-wave form)
+ * from K, N and M; every tile gives the same bits, so the choice is one of speed only.  For tests and tools:
+ * adil_pw_conv_bwd_tile is the same call at the forced tile `bo`; bo outside {64, 128, 256, 512}, K % bo != 0, or
+ * bo >= 256 with g3 set (the wide tiles have no g3 form): ADIL_EINVAL before any launch, outputs untouched.
+ * adil_pw_route_policy sets how adil_pw_conv_bwd chooses (a host-side int read at launch; 0 = the measured table, the
+ * default; 1 = the narrow tiles 128 / 64 everywhere; 2 = the widest tile dividing K wherever one covers the call) and
+ * returns the previous value; any other argument changes nothing and only returns the current value. */
+int adil_pw_conv_bwd_tile(const void* g, const void* g2, const void* y, const float* scale, const void* wt, void* gx,
+                          void* gres, int M, int K, int N, int relu, const void* xin, const float* pscale,
+                          const float* pshift, const void* g3, int sub_w, int sub_hw, void* stream, int bo);
+int adil_pw_route_policy(int policy);
 
 /* Residual join of two consecutive bottlenecks of one stage (conv3 of block i-1 and conv1 of block i) as ONE kernel;
  * the C-channel tensor between the two GEMMs is kept on chip.  W = width in {64, 128}, C = 4 W, M = pixels; bf16

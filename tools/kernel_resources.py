@@ -28,6 +28,6 @@ if "error" in out and not rows:
 demangle = subprocess.run(["c++filt"] + [r["name"] for r in rows], capture_output=True, text=True).stdout.splitlines()
 print(f"{'kernel':90s} vgpr agpr spill occ scratch")
 for r, d in zip(rows, demangle):
-    d = re.sub(r"\(.*", "", d).replace("void ", "")
+    d = re.sub(r"\(.*", "", d.replace("(anonymous namespace)::", "")).replace("void ", "")
     if flt in d:
         print(f"{d[:90]:90s} {r.get('vgpr', 0):4d} {r.get('agpr', 0):4d} {r.get('spill', 0):5d} {r.get('occ', 0):3d} {r.get('scratch', 0):7d}")
