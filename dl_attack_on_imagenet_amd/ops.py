@@ -1205,6 +1205,68 @@ def dense1x1_conv(x: Tensor, pscale: Tensor, pshift: Tensor, w2d: Tensor, wt2d: 
 
 
 # --------------------------------------------------------------------------- #
+DENSE3X3_MAX_W = 63          # ADIL_DENSE3X3_MAX_W of include/adil_hip.h
+DENSE3X3_CHANNELS = range(32, 512 + 1, 32)   # channel counts of adil_dense3x3_fwd / _bwd, either side
+
+
+def dense3x3_covers(x: Tensor, cin: int, cout: int) -> bool:
+    """What adil_dense3x3_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == cin and cin in DENSE3X3_CHANNELS
+            and cout in DENSE3X3_CHANNELS and 0 < x.shape[3] <= DENSE3X3_MAX_W and x.shape[2] > 0
+            and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+
+
+class Dense3x3Function(torch.autograd.Function):
+    """3x3 / stride 1 / pad 1 convolution with 32-channel granularity on channels_last bf16 tensors, raw output
+    (adil_dense3x3_fwd), and its input gradient on the flipped / transposed weights (adil_dense3x3_bwd).  No weight
+    gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, wp_fwd, wp_bwd):
+        lib = _lib.load()
+        b, c, h, w = x.shape
+        n = wp_fwd.shape[0]
+        x2 = _nhwc(x)
+        y = torch.empty((b, h, w, n), dtype=torch.bfloat16, device=x.device)
+        if b > 0:
+            _lib.check(lib.adil_dense3x3_fwd(_ptr(x2), _ptr(wp_fwd), _ptr(y), b, h, w, c, n, _stream()), "adil_dense3x3_fwd")
+        ctx.save_for_backward(wp_bwd)
+        ctx.meta = (c,)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        (wp_bwd,) = ctx.saved_tensors
+        (c,) = ctx.meta
+        g2 = _nhwc_grad(g)
+        b, h, w, n = g2.shape
+        gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
+        if b > 0:
+            _lib.check(lib.adil_dense3x3_bwd(_ptr(g2), _ptr(wp_bwd), _ptr(gx), b, h, w, c, n, _stream()), "adil_dense3x3_bwd")
+        return gx.permute(0, 3, 1, 2), None, None
+
+
+def dense3x3_conv(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
+    """x (B,C,H,W) bf16 in channels_last memory format -> its 3x3 / stride 1 / pad 1 convolution as (B,N,H,W), same
+    format, no copies.  wp_fwd (N, 9*C) and wp_bwd (C, 9*N) bf16 are the two layouts of `pack_conv3x3_weights`."""
+    if wp_fwd.dim() != 2 or wp_bwd.dim() != 2 or wp_bwd.shape[0] == 0 or wp_fwd.shape[1] != 9 * wp_bwd.shape[0]:
+        raise ValueError(f"wp_fwd / wp_bwd must be the (N, 9C) / (C, 9N) matrices of pack_conv3x3_weights, got "
+                         f"{tuple(wp_fwd.shape)} / {tuple(wp_bwd.shape)}")
+    n, c = wp_fwd.shape[0], wp_bwd.shape[0]
+    if x.dim() == 4 and x.shape[0] == 0:                  # an empty batch is no kernel limit
+        if not (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == c):
+            raise ValueError(f"adil_dense3x3 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
+    elif not dense3x3_covers(x, c, n):
+        raise ValueError(f"adil_dense3x3 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with a "
+                         f"{n} x {c} x 3 x 3 weight")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError("x must be in channels_last memory format (the kernels read it in place)")
+    _check_operands(x.device, ("wp_fwd", wp_fwd, (n, 9 * c), torch.bfloat16), ("wp_bwd", wp_bwd, (c, 9 * n), torch.bfloat16))
+    return Dense3x3Function.apply(x, wp_fwd, wp_bwd)
+
+
+# --------------------------------------------------------------------------- #
 def pack_stem_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
     """(64,3,7,7) conv weight -> the two bf16 layouts of include/adil_hip.h: w_fwd [64][7][8][4], w_bwd [4][49][64]."""
     if tuple(weight.shape) != (64, 3, 7, 7):

@@ -906,6 +906,45 @@ def use_own_dense_pointwise_(net: nn.Module) -> int:
             + _rewrite_children_(net, _is_transition, _OwnTransition))
 
 
+class _OwnGrowthConv(nn.Module):
+    """The 3x3 growth convolution of a dense layer (`conv2`) on `ops.dense3x3_conv` where the kernel covers the input.
+    `weight` stays the parameter (same state_dict key as the `Conv2d` it replaces); `wp_fwd` / `wp_bwd` are its two packed
+    layouts as non-persistent buffers (no state_dict entries), cast with the network and 2-D, so channels_last leaves
+    them alone.  Every other input (CPU, fp32, not channels_last, W > 63) gets `F.conv2d` on the weight."""
+
+    def __init__(self, conv: nn.Conv2d):
+        super().__init__()
+        if not _is_growth_conv(conv):
+            raise ValueError("not a 3x3 / stride 1 / pad 1 convolution with channel counts the dense3x3 kernels cover")
+        self.in_channels, self.out_channels = conv.in_channels, conv.out_channels
+        self.weight = conv.weight
+        wp_fwd, wp_bwd = ops.pack_conv3x3_weights(conv.weight)
+        self.register_buffer('wp_fwd', wp_fwd, persistent=False)
+        self.register_buffer('wp_bwd', wp_bwd, persistent=False)
+
+    def forward(self, x):
+        if (ops.dense3x3_covers(x, self.in_channels, self.out_channels) and x.is_contiguous(memory_format=torch.channels_last)
+                and self.wp_fwd.dtype == torch.bfloat16 and self.wp_fwd.device == x.device and self.wp_bwd.device == x.device):
+            return ops.dense3x3_conv(x, self.wp_fwd, self.wp_bwd)
+        return F.conv2d(x, self.weight, None, 1, 1)
+
+
+def _is_growth_conv(conv) -> bool:
+    return (_plain_conv(conv, 3, (1,), 1) and conv.in_channels in ops.DENSE3X3_CHANNELS
+            and conv.out_channels in ops.DENSE3X3_CHANNELS)
+
+
+def use_own_dense_conv_(net: nn.Module) -> int:
+    """Replace `conv2` of every `_DenseLayer` and `_OwnDenseLayer` of the network by an `_OwnGrowthConv`; returns how many
+    were rewritten (DenseNet-121: 58).  Independent of `use_own_dense_pointwise_`, in either order."""
+    n = 0
+    for layer in list(net.modules()):
+        if isinstance(layer, (_DenseLayer, _OwnDenseLayer)) and _is_growth_conv(layer._modules.get('conv2')):
+            layer._modules['conv2'] = _OwnGrowthConv(layer.conv2)
+            n += 1
+    return n
+
+
 def _is_first_conv_block(block) -> bool:
     if not isinstance(block, _ConvBNReLU6) or len(block) != 3:
         return False
@@ -1284,7 +1323,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      fold_bn: bool = False, pad_input_channels: int = 0, fuse_bn_act: bool = False,
                      fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False,
                      own_depthwise: bool = False, own_pointwise: bool = False,
-                     own_first_conv: bool = False, own_dense_pointwise: bool = False) -> nn.Module:
+                     own_first_conv: bool = False, own_dense_pointwise: bool = False,
+                     own_dense_conv: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
@@ -1302,7 +1342,9 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     kernels (`_OwnFirstConv`; the Sequential then holds the network alone, as with fuse_stem; off by default);
     own_dense_pointwise (DenseNet-121, bf16, channels_last) runs the 61 pre-activated 1x1 layers (58 dense layers, 3
     transitions) with the BatchNorm + ReLU in front and behind in the pre-activated pointwise kernels (`_OwnDenseLayer` /
-    `_OwnTransition`; off by default)."""
+    `_OwnTransition`; off by default); own_dense_conv (same conditions, independent of own_dense_pointwise) runs the 58
+    3x3 growth convolutions 128 -> 32 in the 32-channel 3x3 kernels (`_OwnGrowthConv`; off by default).  With both on, the
+    7x7 stem is the only library convolution left in DenseNet-121."""
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
@@ -1333,6 +1375,14 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     if own_dense_pointwise and not channels_last:
         raise ValueError("own_dense_pointwise needs channels_last=True (the pre-activated pointwise kernels work on "
                          "channels_last storage)")
+    if own_dense_conv and key != 'densenet121':
+        raise ValueError("own_dense_conv is a switch of DenseNet-121 (no other network has the growth convolutions "
+                         "rewritten)")
+    if own_dense_conv and dtype != torch.bfloat16:
+        raise ValueError("own_dense_conv needs a bfloat16 network (the 32-channel 3x3 kernels work on bf16 activations)")
+    if own_dense_conv and not channels_last:
+        raise ValueError("own_dense_conv needs channels_last=True (the 32-channel 3x3 kernels work on channels_last "
+                         "storage)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1351,6 +1401,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         stem_fused = True
     if own_dense_pointwise:              # after the weights are loaded: the tables are derived from them
         use_own_dense_pointwise_(net)
+    if own_dense_conv:                   # after the weights are loaded: the packed layouts are derived from them
+        use_own_dense_conv_(net)
     if own_head:                         # after the weights are loaded: the head keeps an fp32 copy of the Linear
         use_own_head_(net, head_fp32)
     if fuse_bn_act and isinstance(net, ResNet):

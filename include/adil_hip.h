@@ -52,7 +52,8 @@ extern "C" {
  * adil_pw_join_bwd, and after them adil_conv3x3_s2_fwd / adil_conv3x3_s2_bwd, were added under 8: new symbols only, no
  * existing signature changed, and a library without them fails to load by name.  adil_dw3x3_fwd / adil_dw3x3_bwd joined them the
  * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those, and
- * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those: all additive
+ * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those, and
+ * adil_dense3x3_fwd / adil_dense3x3_bwd after those: all additive
  * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls neither). */
 int adil_abi_version(void);
 
@@ -516,6 +517,29 @@ int adil_dense1x1_fwd(const void* x, const float* pscale, const float* pshift, c
                       const float* shift, void* y, int M, int K, int N, int act, void* stream);
 int adil_dense1x1_bwd(const void* g, const void* y, const float* scale, const void* wt, const void* xin, const float* pscale,
                       const float* pshift, void* gx, int M, int K, int N, int act, void* stream);
+
+/* 3x3 / stride 1 / pad 1 convolution with 32-channel granularity on either side, forward and input gradient: the growth
+ * convolution (128 -> 32) behind every dense layer of the frozen DenseNet-121, which adil_conv3x3 (C % 64, N % 64) cannot
+ * take.  Semantics of adil_conv3x3: channels_last bf16 storage, raw output, no epilogue.  In BOTH calls C is the layer's
+ * input and N its output channel count, H x W the image:
+ *   adil_dense3x3_fwd : y[B][H][W][N] = sum x[b][h+kh-1][w+kw-1][c] * w[n][c][kh][kw], zero padded;
+ *                       wp [N][9][C] holds w[n][c][kh][kw] at [n][kh*3+kw][c]
+ *   adil_dense3x3_bwd : gx[B][H][W][C] = sum g[b][h+1-kh][w+1-kw][n] * w[n][c][kh][kw];
+ *                       wp_bwd [C][9][N] holds w[n][c][2-kh][2-kw] at [c][kh*3+kw][n]
+ *                       (both layouts are those of adil_conv3x3: ops.pack_conv3x3_weights).  Input gradient only: the
+ *                       network is frozen.
+ * bf16 MFMA with fp32 accumulation in any order, ONE rounding to bf16 (nearest even), a zero sum written as +0.  A tap
+ * that leaves the image (in the linear pixel tiling that includes a tap that would read the neighbouring image of the
+ * batch) contributes nothing BY SELECTION, not by a multiplication with zero: a NaN or Inf in a neighbouring image does
+ * not reach the output.  No atomics: bitwise reproducible.
+ * Limits: C % 32 == 0, N % 32 == 0, 32 <= C, N <= 512, 1 <= W <= ADIL_DENSE3X3_MAX_W, H >= 1, B >= 1,
+ * B H W <= 2^31 - 1, 16-byte aligned pointers.  Anything else, or a NULL pointer: ADIL_EINVAL before any launch, outputs
+ * untouched.  No load or store leaves an operand's extent (the halo rows in front of the first and behind the last pixel
+ * are read at clamped addresses and masked); every element of y / gx is written and nothing behind it.  Element offsets
+ * are 64-bit.  One launch per call on `stream`, no allocation, no synchronisation, no zero-fill launch; capturable. */
+#define ADIL_DENSE3X3_MAX_W 63
+int adil_dense3x3_fwd(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream);
+int adil_dense3x3_bwd(const void* g, const void* wp_bwd, void* gx, int B, int H, int W, int C, int N, void* stream);
 
 #ifdef __cplusplus
 }

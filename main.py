@@ -33,6 +33,10 @@ def build_parser():
     p.add_argument('--own-dense-pointwise', type=int, default=0, choices=[0, 1],
                    help='-m densenet: 1 = a bfloat16 channels_last network whose 61 pre-activated 1x1 layers run in the '
                         'pre-activated pointwise kernels; 0 (default) = the fp32 library network.  Ignored otherwise')
+    p.add_argument('--own-dense-conv', type=int, default=0, choices=[0, 1],
+                   help='-m densenet: 1 = a bfloat16 channels_last network whose 58 3x3 growth convolutions run in the '
+                        '32-channel 3x3 kernels; 0 (default) = the library.  Independent of --own-dense-pointwise.  Ignored '
+                        'otherwise')
     return p
 
 
@@ -43,10 +47,12 @@ def main(args):
     torch.cuda.set_device(0)
     device = torch.device('cuda', 0)
     model_name = args.model.lower()          # names the dictionary file, as upstream (main.py:40, adil.py:89-91)
-    own_dense = bool(args.own_dense_pointwise) and zoo.canonical_name(model_name) == 'densenet121'
+    is_densenet = zoo.canonical_name(model_name) == 'densenet121'
+    own_dense_pw, own_dense_conv = bool(args.own_dense_pointwise) and is_densenet, bool(args.own_dense_conv) and is_densenet
+    own_dense = own_dense_pw or own_dense_conv
     if own_dense:                            # the kernels work on bf16 channels_last activations
         net = zoo.build_classifier(model_name, weights=args.weights, device=device, dtype=torch.bfloat16,
-                                   channels_last=True, own_dense_pointwise=True)
+                                   channels_last=True, own_dense_pointwise=own_dense_pw, own_dense_conv=own_dense_conv)
         model = lambda x: net(x.to(torch.bfloat16)).float()
     else:
         net = model = zoo.build_classifier(model_name, weights=args.weights, device=device)
