@@ -80,6 +80,10 @@ def build_parser():
                    help='-m densenet --dtype bf16: 1 = the 58 3x3 growth convolutions 128 -> 32 run in the 32-channel 3x3 '
                         'kernels on channels_last storage; 0 (default) = the library.  Independent of --own-dense-pointwise; '
                         'with both only the 7x7 stem is left to the library.  Ignored otherwise')
+    p.add_argument('--own-dense-block', type=int, default=0, choices=[0, 1],
+                   help='-m densenet --dtype bf16: 1 = each of the 4 dense blocks runs on one channels_last feature buffer '
+                        '(no torch.cat, input gradients accumulated inside the 1x1 gradient kernel); needs '
+                        '--own-dense-pointwise 1 and --own-dense-conv 1; 0 (default) = per-layer tensors.  Ignored otherwise')
     p.add_argument('--own-first-conv', type=int, default=0, choices=[0, 1],
                    help='-m mobilenet --dtype bf16: 1 = the normalisation and the 3 -> 32 first convolution (with its BatchNorm '
                         'and ReLU6) run in the first-convolution kernels on the attack\'s own tensors; 0 (default) = the '
@@ -158,11 +162,13 @@ def main(args):
                  and zoo.canonical_name(model_name) == 'densenet121')
     own_dense_conv = (bool(args.own_dense_conv) and dtype == torch.bfloat16
                       and zoo.canonical_name(model_name) == 'densenet121')
+    own_dense_block = (bool(args.own_dense_block) and dtype == torch.bfloat16
+                       and zoo.canonical_name(model_name) == 'densenet121')
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
                                  channels_last=(fast or own_dw or own_pw or own_fc or bool(own_head) or own_dense
                                                 or own_dense_conv),
                                  own_depthwise=own_dw, own_pointwise=own_pw, own_dense_pointwise=own_dense,
-                                 own_dense_conv=own_dense_conv,
+                                 own_dense_conv=own_dense_conv, own_dense_block=own_dense_block,
                                  own_first_conv=own_fc, fuse_bn_act=fast,
                                  fuse_stem=fast,
                                  head_fp32="inference" if fast else own_head,   # fp32 logits inside the DDrague inference loop

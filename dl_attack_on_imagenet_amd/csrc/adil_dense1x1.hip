@@ -21,6 +21,13 @@
 //   O are read at a clamped in-range address and replaced by zeros on BOTH operands; a pixel row past M reads row M - 1
 //   and is not stored; a table entry past its extent is read at a clamped index.  The tables are read element-wise
 //   (4-byte alignment is all they need).
+//   Row pitches (the _ld entry points): x / g, y, xin and the output each have a pitch of their own, in elements, at or
+//   above their width; row m of an operand starts at base + m * ld and the columns at or behind the width are never
+//   touched (the clamped reads above stay inside the width).  The weights and the tables are dense.  The plain entry
+//   points pass ld = width.
+//   ACC (gradient only): gx[m][k] = bf16_rne(f32(gx_old[m][k]) + v), v the fp32 value the plain gradient rounds: one fp32
+//   add (never contracted with the product in front of it), one rounding.  The old value is fetched with xin, under the
+//   reduction loop, by the lane that holds the accumulator; the wave that read a pixel row is the wave that writes it.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -45,13 +52,20 @@ __device__ __forceinline__ float d1_pre(float x, float ps, float pb) {
     return p + pb;
 }
 
-template <int CT, bool BWD>
+// the accumulate form's value: the product is rounded to fp32 BEFORE the old gradient is added (no fma)
+__device__ __forceinline__ float d1_mul_add(float t, float ps, float old) {
+#pragma clang fp contract(off)
+    const float v = t * ps;
+    return old + v;
+}
+
+template <int CT, bool BWD, bool ACC>
 __global__ __launch_bounds__(256) void d1_kernel(const bf16_t* __restrict__ a, const bf16_t* __restrict__ yin,
                                                  const bf16_t* __restrict__ bm, const float* __restrict__ rt0,
                                                  const float* __restrict__ rt1, const float* __restrict__ ot0,
                                                  const float* __restrict__ ot1, const bf16_t* __restrict__ xin,
                                                  bf16_t* __restrict__ out, int M, int R, int O, int act, int MT, int OT,
-                                                 int tab_off) {
+                                                 int tab_off, int lda, int ldyin, int ldxin, int ldo) {
     constexpr int BO = 32 * CT;
     constexpr int ACH = D1_BM * D1_BK / 8 / 256;         // 16-byte chunks of the A tile per thread (4)
     constexpr int OS = BO + 8;                           // transposed-output pixel stride (elements)
@@ -97,13 +111,15 @@ __global__ __launch_bounds__(256) void d1_kernel(const bf16_t* __restrict__ a, c
     }
     __syncthreads();
 
-    size_t arow[ACH];
+    const bool masked = BWD && act != 0;
+    size_t arow[ACH], yrow[BWD ? ACH : 1];
 #pragma unroll
     for (int i = 0; i < ACH; ++i) {
         const int row = (tid + 256 * i) >> 3;
-        arow[i] = (size_t)((m0 + row < M) ? m0 + row : M - 1) * (size_t)R;
+        const size_t mr = (size_t)((m0 + row < M) ? m0 + row : M - 1);
+        arow[i] = mr * (size_t)lda;
+        if (BWD) yrow[i] = mr * (size_t)ldyin;
     }
-    const bool masked = BWD && act != 0;
     u32x4 ar[ACH], yr[BWD ? ACH : 1], br[CT];
     const u32x4 zero4 = {0u, 0u, 0u, 0u};
     auto load_tiles = [&](int kc) {
@@ -113,7 +129,7 @@ __global__ __launch_bounds__(256) void d1_kernel(const bf16_t* __restrict__ a, c
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             ar[i] = *reinterpret_cast<const u32x4*>(a + arow[i] + colc);
-            if (masked) yr[i] = *reinterpret_cast<const u32x4*>(yin + arow[i] + colc);
+            if (masked) yr[i] = *reinterpret_cast<const u32x4*>(yin + yrow[i] + colc);
             if (!cok) ar[i] = zero4;
         }
 #pragma unroll
@@ -168,15 +184,17 @@ __global__ __launch_bounds__(256) void d1_kernel(const bf16_t* __restrict__ a, c
     load_tiles(0);
     const int m = m0 + w * 32 + c;                       // this lane's pixel in the epilogue
     // the gradient's xin does not depend on the GEMM: its loads fly under the reduction loop
-    u32x2 xr[BWD ? CT : 1][4];
+    u32x2 xr[BWD ? CT : 1][4], gr[ACC ? CT : 1][4];
     if (BWD) {
-        const bf16_t* xp = xin + (size_t)(m < M ? m : M - 1) * (size_t)O;
+        const bf16_t* xp = xin + (size_t)(m < M ? m : M - 1) * (size_t)ldxin;
+        const bf16_t* gp = out + (size_t)(m < M ? m : M - 1) * (size_t)ldo;        // the old gradient (ACC)
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int n = o0 + 32 * ct + 8 * q + 4 * h;          // O % 8 == 0: the four channels are in or out together
                 xr[ct][q] = *reinterpret_cast<const u32x2*>(xp + (n < O ? n : 0));
+                if (ACC) gr[ct][q] = *reinterpret_cast<const u32x2*>(gp + (n < O ? n : 0));
             }
     }
     f32x16 acc[CT];
@@ -212,11 +230,23 @@ __global__ __launch_bounds__(256) void d1_kernel(const bf16_t* __restrict__ a, c
             if (BWD) {
                 const f32x2 x0 = bf2_to_f32x2(xr[ct][q][0]), x1 = bf2_to_f32x2(xr[ct][q][1]);
                 const float xv[4] = {x0[0], x0[1], x1[0], x1[1]};
+                if (ACC) {
+                    const f32x2 g0 = bf2_to_f32x2(gr[ct][q][0]), g1 = bf2_to_f32x2(gr[ct][q][1]);
+                    const float gv[4] = {g0[0], g0[1], g1[0], g1[1]};
 #pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    const float ps = otab[co + e];
-                    const float pre = d1_pre(xv[e], ps, otab[BO + co + e]);
-                    v[e] = pre > 0.0f ? v[e] * ps : 0.0f;            // the forward's branch; elsewhere +0
+                    for (int e = 0; e < 4; ++e) {
+                        const float ps = otab[co + e];
+                        const float pre = d1_pre(xv[e], ps, otab[BO + co + e]);
+                        // old + v, v = +0 off the forward's branch (an old -0.0 there becomes +0)
+                        v[e] = pre > 0.0f ? d1_mul_add(v[e], ps, gv[e]) : gv[e] + 0.0f;
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const float ps = otab[co + e];
+                        const float pre = d1_pre(xv[e], ps, otab[BO + co + e]);
+                        v[e] = pre > 0.0f ? v[e] * ps : 0.0f;        // the forward's branch; elsewhere +0
+                    }
                 }
             } else {
 #pragma unroll
@@ -238,7 +268,7 @@ __global__ __launch_bounds__(256) void d1_kernel(const bf16_t* __restrict__ a, c
         const int id = lane + 64 * i, px = id / CPP, ch = id - px * CPP;
         const u32x4 t = *reinterpret_cast<const u32x4*>(so + px * OS + ch * 8);
         const int mm = m0 + w * 32 + px, n = o0 + ch * 8;
-        if (mm < M && n < O) *reinterpret_cast<u32x4*>(out + (size_t)mm * (size_t)O + n) = t;
+        if (mm < M && n < O) *reinterpret_cast<u32x4*>(out + (size_t)mm * (size_t)ldo + n) = t;
     }
 }
 
@@ -246,49 +276,87 @@ inline bool d1_dims_ok(int M, int K, int N, int act) {
     return M >= 1 && K >= 8 && N >= 8 && K <= D1_MAXC && N <= D1_MAXC && (K % 8) == 0 && (N % 8) == 0 && (act == 0 || act == 1);
 }
 
-template <int CT, bool BWD>
-void d1_launch(const bf16_t* a, const bf16_t* yin, const bf16_t* bm, const float* rt0, const float* rt1, const float* ot0,
-               const float* ot1, const bf16_t* xin, bf16_t* out, int M, int R, int O, int act, int OT, hipStream_t s) {
+// one call: the operands of the GEMM OUT[M][O] = A'[M][R] . B[O][R]^T with their row pitches (elements)
+struct D1Call {
+    const bf16_t *a, *yin, *bm, *xin;
+    const float *rt0, *rt1, *ot0, *ot1;
+    bf16_t* out;
+    int M, R, O, act, lda, ldyin, ldxin, ldo;
+};
+
+inline bool d1_ld_ok(int ld, int width) { return ld >= width && (ld % 8) == 0; }
+
+template <int CT, bool BWD, bool ACC>
+void d1_launch(const D1Call& c, int OT, hipStream_t s) {
     constexpr int BO = 32 * CT;
     constexpr size_t tiles = (size_t)(D1_BM + BO) * D1_LS * sizeof(bf16_t), trans = (size_t)4 * 32 * (BO + 8) * sizeof(bf16_t);
     constexpr size_t tab_off = tiles > trans ? tiles : trans;            // a multiple of 16 either way
-    const int MT = (M + D1_BM - 1) / D1_BM, RP = (R + D1_BK - 1) / D1_BK * D1_BK;
+    const int MT = (c.M + D1_BM - 1) / D1_BM, RP = (c.R + D1_BK - 1) / D1_BK * D1_BK;
     const size_t tabs = (size_t)(BWD ? 1 : 2) * RP * sizeof(float);
     // widest case (CT = 5, forward, R = 2048): 43008 B of transposed output + 16384 B of tables + 1280 B of static otab
     // = 60672 B of the 64 KiB a workgroup may have
     static_assert(tab_off % 16 == 0 && tab_off + 2 * D1_MAXC * sizeof(float) + 2 * BO * sizeof(float) <= 65536,
                   "tiles + reduction tables + otab must fit the 64 KiB of LDS a workgroup may have");
-    hipLaunchKernelGGL((d1_kernel<CT, BWD>), dim3((unsigned)MT * (unsigned)OT), dim3(256), tab_off + tabs, s, a, yin, bm, rt0,
-                       rt1, ot0, ot1, xin, out, M, R, O, act, MT, OT, (int)tab_off);
+    hipLaunchKernelGGL((d1_kernel<CT, BWD, ACC>), dim3((unsigned)MT * (unsigned)OT), dim3(256), tab_off + tabs, s, c.a, c.yin,
+                       c.bm, c.rt0, c.rt1, c.ot0, c.ot1, c.xin, c.out, c.M, c.R, c.O, c.act, MT, OT, (int)tab_off, c.lda,
+                       c.ldyin, c.ldxin, c.ldo);
 }
 
 // fewest channel tiles of at most 160 channels that cover O, and the narrowest tile that does it
-template <bool BWD>
-void d1_dispatch(const bf16_t* a, const bf16_t* yin, const bf16_t* bm, const float* rt0, const float* rt1, const float* ot0,
-                 const float* ot1, const bf16_t* xin, bf16_t* out, int M, int R, int O, int act, hipStream_t s) {
-    const int OT = (O + 159) / 160, per = (O + OT - 1) / OT, ct = (per + 31) / 32;
+template <bool BWD, bool ACC>
+void d1_dispatch(const D1Call& c, hipStream_t s) {
+    const int OT = (c.O + 159) / 160, per = (c.O + OT - 1) / OT, ct = (per + 31) / 32;
     switch (ct) {
-        case 1: d1_launch<1, BWD>(a, yin, bm, rt0, rt1, ot0, ot1, xin, out, M, R, O, act, OT, s); break;
-        case 2: d1_launch<2, BWD>(a, yin, bm, rt0, rt1, ot0, ot1, xin, out, M, R, O, act, OT, s); break;
-        case 3: d1_launch<3, BWD>(a, yin, bm, rt0, rt1, ot0, ot1, xin, out, M, R, O, act, OT, s); break;
-        case 4: d1_launch<4, BWD>(a, yin, bm, rt0, rt1, ot0, ot1, xin, out, M, R, O, act, OT, s); break;
-        default: d1_launch<5, BWD>(a, yin, bm, rt0, rt1, ot0, ot1, xin, out, M, R, O, act, OT, s); break;
+        case 1: d1_launch<1, BWD, ACC>(c, OT, s); break;
+        case 2: d1_launch<2, BWD, ACC>(c, OT, s); break;
+        case 3: d1_launch<3, BWD, ACC>(c, OT, s); break;
+        case 4: d1_launch<4, BWD, ACC>(c, OT, s); break;
+        default: d1_launch<5, BWD, ACC>(c, OT, s); break;
     }
 }
 
 }  // namespace
 
-extern "C" int adil_dense1x1_fwd(const void* x, const float* pscale, const float* pshift, const void* w, const float* scale,
-                                 const float* shift, void* y, int M, int K, int N, int act, void* stream) {
+extern "C" int adil_dense1x1_fwd_ld(const void* x, int ldx, const float* pscale, const float* pshift, const void* w,
+                                    const float* scale, const float* shift, void* y, int ldy, int M, int K, int N, int act,
+                                    void* stream) {
     if (x == nullptr || pscale == nullptr || pshift == nullptr || w == nullptr || scale == nullptr || shift == nullptr ||
-        y == nullptr || !d1_dims_ok(M, K, N, act))
+        y == nullptr || !d1_dims_ok(M, K, N, act) || !d1_ld_ok(ldx, K) || !d1_ld_ok(ldy, N))
         return ADIL_EINVAL;
     if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y, 16) || !aligned(pscale, 4) || !aligned(pshift, 4) ||
         !aligned(scale, 4) || !aligned(shift, 4))
         return ADIL_EINVAL;
     ADIL_ENTER();
-    d1_dispatch<false>((const bf16_t*)x, nullptr, (const bf16_t*)w, pscale, pshift, scale, shift, nullptr, (bf16_t*)y, M, K, N,
-                       act, (hipStream_t)stream);
+    const D1Call c = {(const bf16_t*)x, nullptr, (const bf16_t*)w, nullptr, pscale, pshift, scale, shift, (bf16_t*)y,
+                      M, K, N, act, ldx, 0, 0, ldy};
+    d1_dispatch<false, false>(c, (hipStream_t)stream);
+    ADIL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int adil_dense1x1_fwd(const void* x, const float* pscale, const float* pshift, const void* w, const float* scale,
+                                 const float* shift, void* y, int M, int K, int N, int act, void* stream) {
+    return adil_dense1x1_fwd_ld(x, K, pscale, pshift, w, scale, shift, y, N, M, K, N, act, stream);
+}
+
+extern "C" int adil_dense1x1_bwd_ld(const void* g, int ldg, const void* y, int ldy, const float* scale, const void* wt,
+                                    const void* xin, int ldxin, const float* pscale, const float* pshift, void* gx, int ldgx,
+                                    int accumulate, int M, int K, int N, int act, void* stream) {
+    if (g == nullptr || scale == nullptr || wt == nullptr || xin == nullptr || pscale == nullptr || pshift == nullptr ||
+        gx == nullptr || !d1_dims_ok(M, K, N, act) || !d1_ld_ok(ldg, N) || !d1_ld_ok(ldy, N) || !d1_ld_ok(ldxin, K) ||
+        !d1_ld_ok(ldgx, K) || (accumulate != 0 && accumulate != 1))
+        return ADIL_EINVAL;
+    if (act != 0 && y == nullptr) return ADIL_EINVAL;
+    if (!aligned(g, 16) || !aligned(wt, 16) || !aligned(xin, 16) || !aligned(gx, 16) || (act != 0 && !aligned(y, 16)) ||
+        !aligned(scale, 4) || !aligned(pscale, 4) || !aligned(pshift, 4))
+        return ADIL_EINVAL;
+    ADIL_ENTER();
+    const D1Call c = {(const bf16_t*)g, act ? (const bf16_t*)y : nullptr, (const bf16_t*)wt, (const bf16_t*)xin, scale, nullptr,
+                      pscale, pshift, (bf16_t*)gx, M, N, K, act, ldg, ldy, ldxin, ldgx};
+    if (accumulate)
+        d1_dispatch<true, true>(c, (hipStream_t)stream);
+    else
+        d1_dispatch<true, false>(c, (hipStream_t)stream);
     ADIL_CHECK_LAUNCH();
     return 0;
 }
@@ -296,16 +364,5 @@ extern "C" int adil_dense1x1_fwd(const void* x, const float* pscale, const float
 extern "C" int adil_dense1x1_bwd(const void* g, const void* y, const float* scale, const void* wt, const void* xin,
                                  const float* pscale, const float* pshift, void* gx, int M, int K, int N, int act,
                                  void* stream) {
-    if (g == nullptr || scale == nullptr || wt == nullptr || xin == nullptr || pscale == nullptr || pshift == nullptr ||
-        gx == nullptr || !d1_dims_ok(M, K, N, act))
-        return ADIL_EINVAL;
-    if (act != 0 && y == nullptr) return ADIL_EINVAL;
-    if (!aligned(g, 16) || !aligned(wt, 16) || !aligned(xin, 16) || !aligned(gx, 16) || (act != 0 && !aligned(y, 16)) ||
-        !aligned(scale, 4) || !aligned(pscale, 4) || !aligned(pshift, 4))
-        return ADIL_EINVAL;
-    ADIL_ENTER();
-    d1_dispatch<true>((const bf16_t*)g, act ? (const bf16_t*)y : nullptr, (const bf16_t*)wt, scale, nullptr, pscale, pshift,
-                      (const bf16_t*)xin, (bf16_t*)gx, M, N, K, act, (hipStream_t)stream);
-    ADIL_CHECK_LAUNCH();
-    return 0;
+    return adil_dense1x1_bwd_ld(g, N, y, N, scale, wt, xin, K, pscale, pshift, gx, K, 0, M, K, N, act, stream);
 }

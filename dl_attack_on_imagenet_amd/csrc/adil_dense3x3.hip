@@ -20,6 +20,9 @@
 //   A halo pixel in front of pixel 0 or behind pixel M - 1 is read at a clamped in-range address; its taps are masked.
 //   A masked tap (off the image: that includes the neighbouring image of the batch) is replaced by zero bits BEFORE the
 //   MFMA, so a NaN or Inf there never meets a multiplier.  A pixel past M is computed on clamped rows and not stored.
+//   Row pitches (the _ld entry points): pixel m of SRC starts at src + m * ldsrc and holds R live channels, pixel m of OUT
+//   at out + m * ldo and holds O; nothing at or behind the width is read or written, so either side may be a channel
+//   slice of a wider channels_last buffer.  The packed weights are dense.  The plain entry points pass the widths.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -38,7 +41,7 @@ namespace {
 template <int CT>
 __global__ __launch_bounds__(256) void d3_kernel(const bf16_t* __restrict__ src, const bf16_t* __restrict__ wp,
                                                  bf16_t* __restrict__ out, int M, int H, int W, int R, int O, int MT,
-                                                 int OT) {
+                                                 int OT, int ldsrc, int ldo) {
     constexpr int BO = 32 * CT;
     constexpr int WROWS = 9 * BO;                          // rows of a weight chunk: tap * BO + o
     constexpr int WCH = (WROWS * 4 + 255) / 256;           // 16-byte chunks of it per thread
@@ -93,7 +96,7 @@ __global__ __launch_bounds__(256) void d3_kernel(const bf16_t* __restrict__ src,
         const int px = (tid + 256 * i) >> 2;
         long long gm = m0 - W - 1 + (px < NP ? px : NP - 1);
         gm = gm < 0 ? 0 : (gm >= M ? (long long)M - 1 : gm);
-        xrow[i] = (size_t)gm * (size_t)R + (size_t)((tid & 3) * 8);
+        xrow[i] = (size_t)gm * (size_t)ldsrc + (size_t)((tid & 3) * 8);
     }
     // the weight rows of this thread (the surplus chunks of the last round read row 0 and are never stored)
     size_t wrow[WCH];
@@ -179,12 +182,13 @@ __global__ __launch_bounds__(256) void d3_kernel(const bf16_t* __restrict__ src,
         const int id = lane + 64 * i, px = id / CPP, ch = id - px * CPP;
         const u32x4 t = *reinterpret_cast<const u32x4*>(so + px * OS + ch * 8);
         const long long mm = m0 + w * 64 + px;
-        if (mm < M) *reinterpret_cast<u32x4*>(out + (size_t)mm * (size_t)O + (size_t)(o0 + ch * 8)) = t;
+        if (mm < M) *reinterpret_cast<u32x4*>(out + (size_t)mm * (size_t)ldo + (size_t)(o0 + ch * 8)) = t;
     }
 }
 
 template <int CT>
-int d3_launch(const void* src, const void* wp, void* out, int M, int H, int W, int R, int O, hipStream_t st) {
+int d3_launch(const void* src, int ldsrc, const void* wp, void* out, int ldo, int M, int H, int W, int R, int O,
+              hipStream_t st) {
     constexpr int BO = 32 * CT;
     constexpr size_t lds = (size_t)(D3_NPMAX + 9 * BO) * D3_LS * sizeof(bf16_t);
     static_assert((size_t)4 * 64 * (BO + 8) * sizeof(bf16_t) <= lds, "the output transpose reuses the tile buffers");
@@ -195,32 +199,44 @@ int d3_launch(const void* src, const void* wp, void* out, int M, int H, int W, i
         if (e != hipSuccess) return (int)e;
     }
     hipLaunchKernelGGL((d3_kernel<CT>), dim3((unsigned)MT * (unsigned)OT), dim3(256), lds, st, (const bf16_t*)src,
-                       (const bf16_t*)wp, (bf16_t*)out, M, H, W, R, O, MT, OT);
+                       (const bf16_t*)wp, (bf16_t*)out, M, H, W, R, O, MT, OT, ldsrc, ldo);
     ADIL_CHECK_LAUNCH();
     return 0;
 }
 
-// R = reduction channels, O = output channels of this direction
-int d3_dispatch(const void* src, const void* wp, void* out, int B, int H, int W, int R, int O, void* stream) {
+// R = reduction channels, O = output channels of this direction; ldsrc / ldo = the row pitches of src / out (elements)
+int d3_dispatch(const void* src, int ldsrc, const void* wp, void* out, int ldo, int B, int H, int W, int R, int O,
+                void* stream) {
     if (src == nullptr || wp == nullptr || out == nullptr || B < 1 || H < 1 || W < 1 || W > ADIL_DENSE3X3_MAX_W || R < 32 ||
         O < 32 || R > 512 || O > 512 || (R % 32) != 0 || (O % 32) != 0)
         return ADIL_EINVAL;
+    if (ldsrc < R || ldo < O || (ldsrc % 8) != 0 || (ldo % 8) != 0) return ADIL_EINVAL;
     if ((long long)B * H > 0x7fffffffLL) return ADIL_EINVAL;
     const long long M = (long long)B * H * W;
     if (M > 0x7fffffffLL) return ADIL_EINVAL;
     if (!aligned(src, 16) || !aligned(wp, 16) || !aligned(out, 16)) return ADIL_EINVAL;
     ADIL_ENTER();
-    if (O % 64 == 0) return d3_launch<2>(src, wp, out, (int)M, H, W, R, O, (hipStream_t)stream);
-    return d3_launch<1>(src, wp, out, (int)M, H, W, R, O, (hipStream_t)stream);
+    if (O % 64 == 0) return d3_launch<2>(src, ldsrc, wp, out, ldo, (int)M, H, W, R, O, (hipStream_t)stream);
+    return d3_launch<1>(src, ldsrc, wp, out, ldo, (int)M, H, W, R, O, (hipStream_t)stream);
 }
 
 }  // namespace
 
+extern "C" int adil_dense3x3_fwd_ld(const void* x, int ldx, const void* wp, void* y, int ldy, int B, int H, int W, int C,
+                                    int N, void* stream) {
+    return d3_dispatch(x, ldx, wp, y, ldy, B, H, W, C, N, stream);
+}
+
+extern "C" int adil_dense3x3_bwd_ld(const void* g, int ldg, const void* wp_bwd, void* gx, int ldgx, int B, int H, int W, int C,
+                                    int N, void* stream) {
+    return d3_dispatch(g, ldg, wp_bwd, gx, ldgx, B, H, W, N, C, stream);
+}
+
 extern "C" int adil_dense3x3_fwd(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream) {
-    return d3_dispatch(x, wp, y, B, H, W, C, N, stream);
+    return d3_dispatch(x, C, wp, y, N, B, H, W, C, N, stream);
 }
 
 extern "C" int adil_dense3x3_bwd(const void* g, const void* wp_bwd, void* gx, int B, int H, int W, int C, int N,
                                  void* stream) {
-    return d3_dispatch(g, wp_bwd, gx, B, H, W, N, C, stream);
+    return d3_dispatch(g, N, wp_bwd, gx, C, B, H, W, N, C, stream);
 }

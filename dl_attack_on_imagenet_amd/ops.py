@@ -1267,6 +1267,129 @@ def dense3x3_conv(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
 
 
 # --------------------------------------------------------------------------- #
+DENSE_BLOCK_LAYER_OPERANDS = 8    # (pscale, pshift, w2d, wt2d, scale, shift, wp_fwd, wp_bwd) per layer
+
+
+def dense_block_covers(x: Tensor, c0: int, n_layers: int, growth: int, mid: int) -> bool:
+    """What `dense_block` accepts: an input the strided kernels cover at every layer of the block.  Layer i reads the
+    first c0 + i * growth channels of the block's buffer through adil_dense1x1_fwd_ld (mid outputs) and writes `growth`
+    channels behind them through adil_dense3x3_fwd_ld, so the widths are those of dense1x1_covers (the widest input,
+    c0 + (n_layers - 1) * growth, included) and of dense3x3_covers; every channel offset is a multiple of 8."""
+    if not (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == c0 and n_layers >= 1):
+        return False
+    widest = c0 + (n_layers - 1) * growth
+    return (c0 in PW8_CHANNELS and widest in PW8_CHANNELS and mid in PW8_CHANNELS and mid in DENSE3X3_CHANNELS
+            and growth in DENSE3X3_CHANNELS and 0 < x.shape[3] <= DENSE3X3_MAX_W and x.shape[2] > 0
+            and 1 <= x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+
+
+class DenseBlockFunction(torch.autograd.Function):
+    """A whole dense block on ONE channels_last feature buffer [B][H][W][Ctot], Ctot = C0 + n * growth, with no
+    torch.cat and no gradient-sum kernels.  off_i = C0 + i * growth, M = B H W.
+
+    Forward: the input is copied into the first C0 channels (the one copy left); layer i reads the off_i-channel prefix
+    in place (adil_dense1x1_fwd_ld, ldx = Ctot, ReLU behind) into mid_i [M][mid] and its growth convolution writes
+    channels [off_i, off_i + growth) of the buffer (adil_dense3x3_fwd_ld, ldy = Ctot).  The values are those of the
+    per-layer path on torch.cat's copies, bit for bit: only addresses differ.  Saved for the backward: the buffer, every
+    mid_i (the ReLU mask of its layer) and the tables; under no_grad one mid is reused.
+
+    Backward: gbuf is a contiguous NHWC COPY of the incoming gradient (g itself is never written).  For i = n-1 .. 0:
+    gmid = adil_dense3x3_bwd_ld(gbuf + off_i, ldg = Ctot), then adil_dense1x1_bwd_ld(gmid, mid_i, xin = the buffer,
+    gx = gbuf, ldgx = Ctot, accumulate = 1, K = off_i) adds layer i's input gradient into the off_i-channel prefix.  So
+    the gradient of a feature is its incoming gradient plus the contributions of its consumers in the order LAST LAYER
+    FIRST, each as one fp32 add of the unrounded fp32 contribution followed by ONE rounding to bf16 (autograd's path
+    rounds every contribution to bf16 and then adds in its own order).  This order and the one-rounding-per-add rule are
+    the specification of this path.  The result is gbuf[..., :C0].  No weight gradient: the network is frozen.  Every
+    launch goes on the current stream; nothing synchronises."""
+
+    @staticmethod
+    def forward(ctx, x, keep, *flat):
+        lib = _lib.load()
+        L = DENSE_BLOCK_LAYER_OPERANDS
+        n = len(flat) // L
+        b, c0, h, w = x.shape
+        mid, growth = flat[2].shape[0], flat[6].shape[0]
+        ctot, m = c0 + n * growth, b * h * w
+        buf = torch.empty((b, h, w, ctot), dtype=torch.bfloat16, device=x.device)
+        buf[..., :c0].copy_(x.permute(0, 2, 3, 1))
+        rows = buf.view(m, ctot)
+        mids = []
+        for i in range(n):
+            pscale, pshift, w2d, _, scale, shift, wp_fwd, _ = flat[L * i:L * i + L]
+            off = c0 + i * growth
+            if keep or not mids:
+                mids.append(torch.empty((m, mid), dtype=torch.bfloat16, device=x.device))
+            t = mids[-1]
+            _lib.check(lib.adil_dense1x1_fwd_ld(_ptr(buf), ctot, _ptr(pscale), _ptr(pshift), _ptr(w2d), _ptr(scale), _ptr(shift),
+                                                _ptr(t), mid, m, off, mid, 1, _stream()), "adil_dense1x1_fwd_ld")
+            _lib.check(lib.adil_dense3x3_fwd_ld(_ptr(t), mid, _ptr(wp_fwd), _ptr(rows[:, off:]), ctot, b, h, w, mid, growth,
+                                                _stream()), "adil_dense3x3_fwd_ld")
+        if keep:
+            ctx.save_for_backward(buf, *mids, *flat)
+        ctx.meta = (n, c0, mid, growth)
+        return buf.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        L = DENSE_BLOCK_LAYER_OPERANDS
+        n, c0, mid, growth = ctx.meta
+        saved = ctx.saved_tensors
+        if not saved:
+            raise RuntimeError("dense_block was run without keeping what its backward needs")
+        buf, mids, flat = saved[0], saved[1:1 + n], saved[1 + n:]
+        if not ctx.needs_input_grad[0]:
+            return (None,) * (2 + len(flat))
+        b, h, w, ctot = buf.shape
+        m = b * h * w
+        gbuf = torch.empty((b, h, w, ctot), dtype=torch.bfloat16, device=buf.device)
+        gbuf.copy_(g.permute(0, 2, 3, 1))
+        grows = gbuf.view(m, ctot)
+        gmid = torch.empty((m, mid), dtype=torch.bfloat16, device=buf.device)
+        for i in range(n - 1, -1, -1):
+            pscale, pshift, _, wt2d, scale, _, _, wp_bwd = flat[L * i:L * i + L]
+            off = c0 + i * growth
+            _lib.check(lib.adil_dense3x3_bwd_ld(_ptr(grows[:, off:]), ctot, _ptr(wp_bwd), _ptr(gmid), mid, b, h, w, mid, growth,
+                                                _stream()), "adil_dense3x3_bwd_ld")
+            _lib.check(lib.adil_dense1x1_bwd_ld(_ptr(gmid), mid, _ptr(mids[i]), mid, _ptr(scale), _ptr(wt2d), _ptr(buf), ctot,
+                                                _ptr(pscale), _ptr(pshift), _ptr(gbuf), ctot, 1, m, off, mid, 1, _stream()),
+                       "adil_dense1x1_bwd_ld")
+        return (gbuf[..., :c0].permute(0, 3, 1, 2), None) + (None,) * len(flat)
+
+
+def dense_block(x: Tensor, layers) -> Tensor:
+    """x (B,C0,H,W) bf16 in channels_last memory format -> the block's (B, C0 + n * growth, H, W) output, channels_last,
+    as torch.cat of the input and the n layer outputs returned it.  `layers` is a sequence of per-layer operand tuples
+    (pscale, pshift, w2d, wt2d, scale, shift, wp_fwd, wp_bwd): the operands of `dense1x1_conv` (with relu) and of
+    `dense3x3_conv` for layer i, whose input width is C0 + i * growth.  See `DenseBlockFunction` for the order of the
+    gradient sums."""
+    layers = [tuple(t) for t in layers]
+    if not layers or any(len(t) != DENSE_BLOCK_LAYER_OPERANDS for t in layers):
+        raise ValueError(f"layers must be a non-empty sequence of {DENSE_BLOCK_LAYER_OPERANDS}-tuples "
+                         "(pscale, pshift, w2d, wt2d, scale, shift, wp_fwd, wp_bwd)")
+    w2d0, wp0 = layers[0][2], layers[0][6]
+    if w2d0.dim() != 2 or wp0.dim() != 2:
+        raise ValueError("w2d must be a (mid, K) matrix and wp_fwd the (growth, 9 * mid) matrix of pack_conv3x3_weights")
+    mid, growth = w2d0.shape[0], wp0.shape[0]
+    c0 = x.shape[1] if x.dim() == 4 else -1
+    if not dense_block_covers(x, c0, len(layers), growth, mid):
+        raise ValueError(f"the strided dense kernels do not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with "
+                         f"{len(layers)} layers of growth {growth} and width {mid}")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError("x must be in channels_last memory format")
+    for i, (pscale, pshift, w2d, wt2d, scale, shift, wp_fwd, wp_bwd) in enumerate(layers):
+        k = c0 + i * growth
+        _check_operands(x.device, (f"layers[{i}].pscale", pscale, (k,), torch.float32),
+                        (f"layers[{i}].pshift", pshift, (k,), torch.float32),
+                        (f"layers[{i}].w2d", w2d, (mid, k), torch.bfloat16), (f"layers[{i}].wt2d", wt2d, (k, mid), torch.bfloat16),
+                        (f"layers[{i}].scale", scale, (mid,), torch.float32), (f"layers[{i}].shift", shift, (mid,), torch.float32),
+                        (f"layers[{i}].wp_fwd", wp_fwd, (growth, 9 * mid), torch.bfloat16),
+                        (f"layers[{i}].wp_bwd", wp_bwd, (mid, 9 * growth), torch.bfloat16))
+    keep = torch.is_grad_enabled() and x.requires_grad
+    return DenseBlockFunction.apply(x, keep, *[t for layer in layers for t in layer])
+
+
+# --------------------------------------------------------------------------- #
 def pack_stem_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
     """(64,3,7,7) conv weight -> the two bf16 layouts of include/adil_hip.h: w_fwd [64][7][8][4], w_bwd [4][49][64]."""
     if tuple(weight.shape) != (64, 3, 7, 7):

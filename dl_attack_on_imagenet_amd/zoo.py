@@ -945,6 +945,66 @@ def use_own_dense_conv_(net: nn.Module) -> int:
     return n
 
 
+def _is_own_dense_block(block) -> bool:
+    """A block whose every child is an `_OwnDenseLayer` with an `_OwnGrowthConv` as conv2, all of one growth and one
+    bottleneck width, on consecutive input widths (each layer reads what the one before it read plus its output)."""
+    layers = list(block.values()) if isinstance(block, nn.ModuleDict) else []
+    if not layers or not all(isinstance(m, _OwnDenseLayer) and isinstance(m._modules.get('conv2'), _OwnGrowthConv)
+                             for m in layers):
+        return False
+    growth, mid = layers[0].conv2.out_channels, layers[0].cout
+    return all(m.conv2.out_channels == growth and m.cout == mid and m.conv2.in_channels == mid
+               and m.cin == layers[0].cin + i * growth for i, m in enumerate(layers))
+
+
+class _OwnDenseBlock(nn.ModuleDict):
+    """A `_DenseBlock` of `_OwnDenseLayer`s with `_OwnGrowthConv`s as ONE `ops.dense_block` call where the strided kernels
+    cover the input: the block's features live in one channels_last buffer, no torch.cat, no gradient-sum kernels.  The
+    children keep their names (same state_dict keys); their tables and packed weights are read at call time, nothing is
+    copied here.  Every other input (CPU, fp32, not channels_last, W > 63, tables on another device) runs the loop of
+    `_DenseBlock.forward` over the children."""
+
+    def __init__(self, block: nn.ModuleDict):
+        super().__init__()
+        if not _is_own_dense_block(block):
+            raise ValueError("not a dense block of _OwnDenseLayer children with _OwnGrowthConv growth convolutions")
+        for name, layer in block.items():
+            self.add_module(name, layer)
+
+    def _covers(self, x) -> bool:
+        layers = list(self.values())
+        first = layers[0]
+        if not (x.dim() == 4 and ops.dense_block_covers(x, first.cin, len(layers), first.conv2.out_channels, first.cout)
+                and x.is_contiguous(memory_format=torch.channels_last)):
+            return False
+        return all(m.conv1.weight.dtype == torch.bfloat16 and m.conv1.weight.device == x.device
+                   and m.wt2d.dtype == torch.bfloat16 and m.wt2d.device == x.device
+                   and all(getattr(m, t).dtype == torch.float32 and getattr(m, t).device == x.device
+                           for t in m._KEEP_FP32)
+                   and all(wp.dtype == torch.bfloat16 and wp.device == x.device for wp in (m.conv2.wp_fwd, m.conv2.wp_bwd))
+                   for m in layers)
+
+    def forward(self, x):
+        if self._covers(x):
+            operands = []
+            for m in self.values():
+                w2d = m.conv1.weight.reshape(m.cout, m.cin)
+                if not w2d.is_contiguous():
+                    w2d = w2d.contiguous()
+                operands.append((m.pscale, m.pshift, w2d, m.wt2d, m.scale, m.shift, m.conv2.wp_fwd, m.conv2.wp_bwd))
+            return ops.dense_block(x, operands)
+        feats = [x]
+        for layer in self.values():
+            feats.append(layer(feats))
+        return torch.cat(feats, 1)
+
+
+def use_own_dense_block_(net: nn.Module) -> int:
+    """Replace every `_DenseBlock` that `use_own_dense_pointwise_` and `use_own_dense_conv_` have rewritten throughout by
+    an `_OwnDenseBlock`; returns how many were replaced (DenseNet-121: 4)."""
+    return _rewrite_children_(net, lambda m: isinstance(m, _DenseBlock) and _is_own_dense_block(m), _OwnDenseBlock)
+
+
 def _is_first_conv_block(block) -> bool:
     if not isinstance(block, _ConvBNReLU6) or len(block) != 3:
         return False
@@ -1324,7 +1384,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False,
                      own_depthwise: bool = False, own_pointwise: bool = False,
                      own_first_conv: bool = False, own_dense_pointwise: bool = False,
-                     own_dense_conv: bool = False) -> nn.Module:
+                     own_dense_conv: bool = False, own_dense_block: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
@@ -1344,7 +1404,11 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     transitions) with the BatchNorm + ReLU in front and behind in the pre-activated pointwise kernels (`_OwnDenseLayer` /
     `_OwnTransition`; off by default); own_dense_conv (same conditions, independent of own_dense_pointwise) runs the 58
     3x3 growth convolutions 128 -> 32 in the 32-channel 3x3 kernels (`_OwnGrowthConv`; off by default).  With both on, the
-    7x7 stem is the only library convolution left in DenseNet-121."""
+    7x7 stem is the only library convolution left in DenseNet-121; own_dense_block (needs BOTH of them, hence their
+    conditions) runs each of the 4 dense blocks on one channels_last feature buffer: the 3x3 kernels write their 32
+    channels straight into it, the 1x1 kernels read a prefix of it in place, and the input gradients are accumulated in
+    one gradient buffer inside the 1x1 gradient kernel (`_OwnDenseBlock`, `ops.dense_block`; no torch.cat and no
+    gradient-sum kernels inside a block; off by default)."""
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
@@ -1383,6 +1447,11 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     if own_dense_conv and not channels_last:
         raise ValueError("own_dense_conv needs channels_last=True (the 32-channel 3x3 kernels work on channels_last "
                          "storage)")
+    if own_dense_block and key != 'densenet121':
+        raise ValueError("own_dense_block is a switch of DenseNet-121 (no other network has dense blocks)")
+    if own_dense_block and not (own_dense_pointwise and own_dense_conv):
+        raise ValueError("own_dense_block needs own_dense_pointwise=True and own_dense_conv=True (the block buffer is read "
+                         "and written by their kernels)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1403,6 +1472,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         use_own_dense_pointwise_(net)
     if own_dense_conv:                   # after the weights are loaded: the packed layouts are derived from them
         use_own_dense_conv_(net)
+    if own_dense_block:                  # after the other two: it takes over the layers they have rewritten
+        use_own_dense_block_(net)
     if own_head:                         # after the weights are loaded: the head keeps an fp32 copy of the Linear
         use_own_head_(net, head_fp32)
     if fuse_bn_act and isinstance(net, ResNet):

@@ -53,7 +53,8 @@ extern "C" {
  * existing signature changed, and a library without them fails to load by name.  adil_dw3x3_fwd / adil_dw3x3_bwd joined them the
  * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those, and
  * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those, and
- * adil_dense3x3_fwd / adil_dense3x3_bwd after those: all additive
+ * adil_dense3x3_fwd / adil_dense3x3_bwd after those, and their row-pitch forms adil_dense1x1_fwd_ld / adil_dense1x1_bwd_ld /
+ * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those: all additive
  * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls neither). */
 int adil_abi_version(void);
 
@@ -517,6 +518,27 @@ int adil_dense1x1_fwd(const void* x, const float* pscale, const float* pshift, c
                       const float* shift, void* y, int M, int K, int N, int act, void* stream);
 int adil_dense1x1_bwd(const void* g, const void* y, const float* scale, const void* wt, const void* xin, const float* pscale,
                       const float* pshift, void* gx, int M, int K, int N, int act, void* stream);
+/* The same two calls on operands that are column slices of wider channels_last buffers (the feature buffer
+ * [B][H][W][Ctot] of a dense block and its gradient buffer).  Every ld* is a row pitch in ELEMENTS: row m of a strided
+ * operand starts at base + m * ld and only its first `width` elements belong to the operand (width = K for x, xin, gx;
+ * N for y, g).  Columns at or behind the width are never read (the zero-filled 16-byte chunk past the reduction extent
+ * is read at an address inside the width) and, on the output, never written: in the gradient buffer they hold the live
+ * gradients of other slices.  w, wt and the tables stay dense.  Everything else is the plain call, which IS this one at
+ * ld = width and accumulate = 0 (same launcher, same bits).
+ *   accumulate (adil_dense1x1_bwd_ld): 0 = gx is written as by adil_dense1x1_bwd.  1 = gx[m][k] = bf16_rne(f32(gx_old[m][k])
+ *     + v) with v the fp32 value t * pscale[k] where pre[m][k] > 0 and +0.0f elsewhere: ONE fp32 add (not contracted with
+ *     the product) and ONE rounding to bf16; v itself is never rounded to bf16.  An old -0.0 under a masked element becomes
+ *     +0.  Every element of the K-wide prefix of a row is read once and written once, by the wave that owns the pixel
+ *     row; no atomics, bitwise reproducible.
+ * Limits: those of the plain calls, and every ld >= its operand's width, every ld % 8 == 0 (16-byte rows), accumulate in
+ * {0, 1} (ldy is checked also where y may be NULL).  Anything else: ADIL_EINVAL before any launch, outputs untouched.
+ * Element offsets are 64-bit (m * ld).  One launch per call, no allocation; capturable. */
+int adil_dense1x1_fwd_ld(const void* x, int ldx, const float* pscale, const float* pshift, const void* w,
+                         const float* scale, const float* shift, void* y, int ldy,
+                         int M, int K, int N, int act, void* stream);
+int adil_dense1x1_bwd_ld(const void* g, int ldg, const void* y, int ldy, const float* scale, const void* wt,
+                         const void* xin, int ldxin, const float* pscale, const float* pshift,
+                         void* gx, int ldgx, int accumulate, int M, int K, int N, int act, void* stream);
 
 /* 3x3 / stride 1 / pad 1 convolution with 32-channel granularity on either side, forward and input gradient: the growth
  * convolution (128 -> 32) behind every dense layer of the frozen DenseNet-121, which adil_conv3x3 (C % 64, N % 64) cannot
@@ -540,6 +562,15 @@ int adil_dense1x1_bwd(const void* g, const void* y, const float* scale, const vo
 #define ADIL_DENSE3X3_MAX_W 63
 int adil_dense3x3_fwd(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream);
 int adil_dense3x3_bwd(const void* g, const void* wp_bwd, void* gx, int B, int H, int W, int C, int N, void* stream);
+/* The same two calls on pixel rows with a pitch: pixel m of x / g starts at base + m * ld (elements) and holds C / N live
+ * channels, pixel m of y / gx likewise with N / C.  Nothing at or behind the width is read (halo rows included) or
+ * written, so the 32-channel side can be a slice of a dense block's feature or gradient buffer.  wp / wp_bwd stay dense.
+ * Limits of the plain calls, and ld >= width, ld % 8 == 0; else ADIL_EINVAL before any launch.  The plain calls are these
+ * at ld = width (same launcher, same bits). */
+int adil_dense3x3_fwd_ld(const void* x, int ldx, const void* wp, void* y, int ldy,
+                         int B, int H, int W, int C, int N, void* stream);
+int adil_dense3x3_bwd_ld(const void* g, int ldg, const void* wp_bwd, void* gx, int ldgx,
+                         int B, int H, int W, int C, int N, void* stream);
 
 #ifdef __cplusplus
 }

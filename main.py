@@ -37,6 +37,10 @@ def build_parser():
                    help='-m densenet: 1 = a bfloat16 channels_last network whose 58 3x3 growth convolutions run in the '
                         '32-channel 3x3 kernels; 0 (default) = the library.  Independent of --own-dense-pointwise.  Ignored '
                         'otherwise')
+    p.add_argument('--own-dense-block', type=int, default=0, choices=[0, 1],
+                   help='-m densenet: 1 = each of the 4 dense blocks runs on one channels_last feature buffer (no torch.cat, '
+                        'input gradients accumulated inside the 1x1 gradient kernel); needs --own-dense-pointwise 1 and '
+                        '--own-dense-conv 1; 0 (default) = per-layer tensors.  Ignored otherwise')
     return p
 
 
@@ -49,10 +53,12 @@ def main(args):
     model_name = args.model.lower()          # names the dictionary file, as upstream (main.py:40, adil.py:89-91)
     is_densenet = zoo.canonical_name(model_name) == 'densenet121'
     own_dense_pw, own_dense_conv = bool(args.own_dense_pointwise) and is_densenet, bool(args.own_dense_conv) and is_densenet
-    own_dense = own_dense_pw or own_dense_conv
+    own_dense_block = bool(args.own_dense_block) and is_densenet
+    own_dense = own_dense_pw or own_dense_conv or own_dense_block
     if own_dense:                            # the kernels work on bf16 channels_last activations
         net = zoo.build_classifier(model_name, weights=args.weights, device=device, dtype=torch.bfloat16,
-                                   channels_last=True, own_dense_pointwise=own_dense_pw, own_dense_conv=own_dense_conv)
+                                   channels_last=True, own_dense_pointwise=own_dense_pw, own_dense_conv=own_dense_conv,
+                                   own_dense_block=own_dense_block)
         model = lambda x: net(x.to(torch.bfloat16)).float()
     else:
         net = model = zoo.build_classifier(model_name, weights=args.weights, device=device)
