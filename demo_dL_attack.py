@@ -84,6 +84,14 @@ def build_parser():
                    help='-m densenet --dtype bf16: 1 = each of the 4 dense blocks runs on one channels_last feature buffer '
                         '(no torch.cat, input gradients accumulated inside the 1x1 gradient kernel); needs '
                         '--own-dense-pointwise 1 and --own-dense-conv 1; 0 (default) = per-layer tensors.  Ignored otherwise')
+    p.add_argument('--own-dense-transition', type=int, default=0, choices=[0, 1],
+                   help='-m densenet --dtype bf16: 1 = each of the 3 transitions runs as one kernel that pools in front of '
+                        'the 1x1 convolution (a quarter of the GEMM, no full-resolution intermediate); needs '
+                        '--own-dense-pointwise 1; 0 (default) = the 1x1 kernel and the library pool.  Ignored otherwise')
+    p.add_argument('--own-dense-stem', type=int, default=0, choices=[0, 1],
+                   help='-m densenet --dtype bf16: 1 = the normalisation and conv0 / norm0 / relu0 / pool0 run in the stem '
+                        'kernels on the attack\'s own tensors; 0 (default) = the library.  Independent of the other dense '
+                        'switches; with all five no library convolution or pooling is left in the trunk.  Ignored otherwise')
     p.add_argument('--own-first-conv', type=int, default=0, choices=[0, 1],
                    help='-m mobilenet --dtype bf16: 1 = the normalisation and the 3 -> 32 first convolution (with its BatchNorm '
                         'and ReLU6) run in the first-convolution kernels on the attack\'s own tensors; 0 (default) = the '
@@ -164,9 +172,14 @@ def main(args):
                       and zoo.canonical_name(model_name) == 'densenet121')
     own_dense_block = (bool(args.own_dense_block) and dtype == torch.bfloat16
                        and zoo.canonical_name(model_name) == 'densenet121')
+    own_dense_transition = (bool(args.own_dense_transition) and dtype == torch.bfloat16
+                            and zoo.canonical_name(model_name) == 'densenet121')
+    own_dense_stem = (bool(args.own_dense_stem) and dtype == torch.bfloat16
+                      and zoo.canonical_name(model_name) == 'densenet121')
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
                                  channels_last=(fast or own_dw or own_pw or own_fc or bool(own_head) or own_dense
-                                                or own_dense_conv),
+                                                or own_dense_conv or own_dense_stem),
+                                 own_dense_transition=own_dense_transition, own_dense_stem=own_dense_stem,
                                  own_depthwise=own_dw, own_pointwise=own_pw, own_dense_pointwise=own_dense,
                                  own_dense_conv=own_dense_conv, own_dense_block=own_dense_block,
                                  own_first_conv=own_fc, fuse_bn_act=fast,

@@ -102,6 +102,10 @@ SIGNATURES = {
                                      c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "adil_dense3x3_fwd_ld": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "adil_dense3x3_bwd_ld": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "adil_dense_transition_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                          c_void_p]),
+    "adil_dense_transition_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                          c_int, c_int, c_int, c_void_p]),
 }
 
 ABI_VERSION = 8

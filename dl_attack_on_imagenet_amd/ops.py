@@ -1205,6 +1205,81 @@ def dense1x1_conv(x: Tensor, pscale: Tensor, pshift: Tensor, w2d: Tensor, wt2d: 
 
 
 # --------------------------------------------------------------------------- #
+def dense_transition_covers(x: Tensor, cin: int, cout: int) -> bool:
+    """What adil_dense_transition_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the path it has):
+    the limits of adil_dense1x1_* and an even H and W."""
+    return (dense1x1_covers(x, cin, cout) and x.shape[2] >= 2 and x.shape[3] >= 2 and x.shape[2] % 2 == 0
+            and x.shape[3] % 2 == 0)
+
+
+def _strided_rows(g: Tensor, n: int):
+    """An incoming (B,N,H,W) gradient as (tensor, row pitch) for a kernel that reads pixel rows at a pitch: the tensor
+    itself where its NHWC view is bf16 rows of N live elements at a pitch ld >= N, ld % 8 == 0, on a 16-byte aligned
+    address (a contiguous channels_last gradient, or the first channels of a wider channels_last buffer: no copy); else
+    the contiguous copy of `_nhwc_grad` at pitch N."""
+    g2 = g.permute(0, 2, 3, 1)
+    b, h, w, _ = g2.shape
+    sb, sh, sw, sc = g2.stride()
+    if (g2.dtype == torch.bfloat16 and sc == 1 and sw >= n and sw % 8 == 0 and (h == 1 or sh == w * sw)
+            and (b == 1 or sb == h * w * sw) and g2.data_ptr() % 16 == 0):
+        return g2, sw
+    return _nhwc_grad(g), n
+
+
+class DenseTransitionFunction(torch.autograd.Function):
+    """eval-BatchNorm + ReLU + AvgPool2d(2, 2) + 1x1 convolution — the transition of a DenseNet with the pooling moved in
+    front of the convolution, with which it commutes — on channels_last bf16 tensors as one GEMM kernel on the pooled
+    pixels (adil_dense_transition_fwd); the input gradient recomputes each input pixel's ReLU branch from the saved input
+    (adil_dense_transition_bwd) and reads a gradient that is a channel slice of a wider buffer in place.  No weight
+    gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, pscale, pshift, w2d, wt2d):
+        lib = _lib.load()
+        b, k, h, w = x.shape
+        n = w2d.shape[0]
+        x2 = _nhwc(x)
+        y = torch.empty((b, h // 2, w // 2, n), dtype=torch.bfloat16, device=x.device)
+        _lib.check(lib.adil_dense_transition_fwd(_ptr(x2), _ptr(pscale), _ptr(pshift), _ptr(w2d), _ptr(y), b, h, w, k, n,
+                                                 _stream()), "adil_dense_transition_fwd")
+        ctx.save_for_backward(x2, pscale, pshift, wt2d)
+        ctx.meta = (b, h, w, k, n)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x2, pscale, pshift, wt2d = ctx.saved_tensors
+        b, h, w, k, n = ctx.meta
+        gx = None
+        if ctx.needs_input_grad[0]:
+            g2, ldg = _strided_rows(g, n)
+            gx = torch.empty((b, h, w, k), dtype=torch.bfloat16, device=g2.device)
+            _lib.check(lib.adil_dense_transition_bwd(_ptr(g2), ldg, _ptr(wt2d), _ptr(x2), _ptr(pscale), _ptr(pshift), _ptr(gx),
+                                                     b, h, w, k, n, _stream()), "adil_dense_transition_bwd")
+            gx = gx.permute(0, 3, 1, 2)
+        return gx, None, None, None, None
+
+
+def dense_transition(x: Tensor, pscale: Tensor, pshift: Tensor, w2d: Tensor, wt2d: Tensor) -> Tensor:
+    """x (B,K,H,W) bf16 in channels_last memory format, H and W even -> avg_pool2d(relu(x * pscale + pshift), 2) . w2d^T
+    as (B,N,H/2,W/2), same format, no copies: the function of BatchNorm -> ReLU -> conv 1x1 -> AvgPool2d(2, 2).  pscale /
+    pshift (K,) fp32, w2d (N,K) and its transpose wt2d (K,N) bf16."""
+    if w2d.dim() != 2:
+        raise ValueError(f"w2d must be a (N, K) matrix, got {tuple(w2d.shape)}")
+    n, k = w2d.shape
+    if not dense_transition_covers(x, k, n):
+        raise ValueError(f"adil_dense_transition does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with a "
+                         f"{n} x {k} weight")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError("x must be in channels_last memory format (the kernels read it in place and the backward reads the "
+                         "saved x itself)")
+    _check_operands(x.device, ("pscale", pscale, (k,), torch.float32), ("pshift", pshift, (k,), torch.float32),
+                    ("w2d", w2d, (n, k), torch.bfloat16), ("wt2d", wt2d, (k, n), torch.bfloat16))
+    return DenseTransitionFunction.apply(x, pscale, pshift, w2d, wt2d)
+
+
+# --------------------------------------------------------------------------- #
 DENSE3X3_MAX_W = 63          # ADIL_DENSE3X3_MAX_W of include/adil_hip.h
 DENSE3X3_CHANNELS = range(32, 512 + 1, 32)   # channel counts of adil_dense3x3_fwd / _bwd, either side
 

@@ -893,8 +893,23 @@ class _OwnTransition(_Dense1x1Tables):
             self.add_module(name, getattr(block, name))
         self._init_tables(self.norm, self.conv, None)
 
+    pool_first = False      # `use_own_dense_transition_` turns it on
+
+    def _pools_first(self, x) -> bool:
+        """The whole transition as ONE `ops.dense_transition` call: a 2 x 2 / stride 2 average pool without padding on an
+        even H and W commutes with the 1x1 convolution."""
+        p = self.pool
+        return (self.pool_first and isinstance(p, nn.AvgPool2d) and p.kernel_size in (2, (2, 2)) and p.stride in (2, (2, 2))
+                and p.padding in (0, (0, 0)) and not p.ceil_mode and p.divisor_override is None
+                and ops.dense_transition_covers(x, self.cin, self.cout))
+
     def forward(self, x):
         if self._covers(x, self.conv):
+            if self._pools_first(x):
+                w2d = self.conv.weight.reshape(self.cout, self.cin)
+                if not w2d.is_contiguous():
+                    w2d = w2d.contiguous()
+                return ops.dense_transition(x, self.pscale, self.pshift, w2d, self.wt2d)
             return self.pool(self._dense1x1(x, self.conv, False))
         return self.pool(self.conv(self.relu(self.norm(x))))
 
@@ -904,6 +919,19 @@ def use_own_dense_pointwise_(net: nn.Module) -> int:
     returns how many 1x1 layers were rewritten (DenseNet-121: 58 dense layers and 3 transitions)."""
     return (_rewrite_children_(net, _is_dense_layer, _OwnDenseLayer)
             + _rewrite_children_(net, _is_transition, _OwnTransition))
+
+
+def use_own_dense_transition_(net: nn.Module) -> int:
+    """Let every `_OwnTransition` of the network (`use_own_dense_pointwise_` creates them) pool in front of its
+    convolution (`ops.dense_transition`: BatchNorm, ReLU, pool and convolution as one kernel on a quarter of the pixels)
+    where the kernel covers the input and the pool is AvgPool2d(2, 2); every other input takes the path it took before.
+    Returns how many were switched (DenseNet-121: 3).  Independent of `use_own_dense_conv_` and `use_own_dense_block_`."""
+    n = 0
+    for m in net.modules():
+        if isinstance(m, _OwnTransition):
+            m.pool_first = True
+            n += 1
+    return n
 
 
 class _OwnGrowthConv(nn.Module):
@@ -1214,6 +1242,70 @@ class _FusedStem(_Fp32Tables):
         return ops.resnet_stem(x, self.w_fwd, self.w_bwd, self.scale, self.shift, self.mean, self.inv_std)
 
 
+def _is_dense_stem(features) -> bool:
+    mods = getattr(features, '_modules', {})
+    if type(features) is not nn.Sequential or list(mods)[:4] != ['conv0', 'norm0', 'relu0', 'pool0']:
+        return False
+    conv, bn, relu, pool = mods['conv0'], mods['norm0'], mods['relu0'], mods['pool0']
+    return (_plain_conv(conv, 7, (2,), 1) and conv.padding == (3, 3) and conv.in_channels == 3 and conv.out_channels == 64
+            and isinstance(bn, nn.BatchNorm2d) and isinstance(relu, nn.ReLU) and isinstance(pool, nn.MaxPool2d)
+            and pool.kernel_size in (3, (3, 3)) and pool.stride in (2, (2, 2)) and pool.padding in (1, (1, 1))
+            and pool.dilation in (1, (1, 1)) and not pool.ceil_mode and not pool.return_indices)
+
+
+class _OwnDenseStem(_KeepsFp32, nn.Sequential):
+    """`features` of a DenseNet whose `conv0 7x7/2 -> norm0 -> relu0 -> pool0 (MaxPool 3/2/1)`, together with the
+    `Normalize` in front of the network, run as the stem kernels (`ops.resnet_stem`: the ResNet stem has this topology)
+    on the attack's own (B,3,H,W) fp32 / bf16 tensor where they cover the input; the children behind `pool0` follow.
+    The children keep their names (same state_dict keys); on every other input (CPU, fp32 network, odd H or W) the module
+    normalises in torch exactly as `Normalize` does and runs all of them, so the rewritten network is the same function
+    everywhere.  Non-persistent buffers (no state_dict entries): `scale` / `shift` from `_bn_affine`; the packed weights
+    `w_fwd` / `w_bwd` and the `Normalize` tables `norm_mean` / `norm_std`, cast with the network."""
+    _KEEP_FP32 = ('scale', 'shift')
+
+    def __init__(self, features: nn.Sequential, mean, std):
+        if not _is_dense_stem(features):
+            raise ValueError("not a conv 3 -> 64 7x7/2 pad 3 + BatchNorm + ReLU + MaxPool2d(3, 2, 1) stem")
+        super().__init__(OrderedDict(features.named_children()))
+        conv, bn = self.conv0, self.norm0
+        w_fwd, w_bwd = ops.pack_stem_weights(conv.weight)
+        _init_norm_affine(self, bn, mean, std, persistent=False)
+        for name, t in (('w_fwd', w_fwd), ('w_bwd', w_bwd),
+                        ('norm_mean', torch.tensor(self.mean, dtype=torch.float32, device=conv.weight.device)),
+                        ('norm_std', torch.tensor([float(v) for v in std], dtype=torch.float32, device=conv.weight.device))):
+            self.register_buffer(name, t, persistent=False)
+
+    def _covers(self, x) -> bool:
+        return (x.dim() == 4 and x.is_cuda and x.shape[1] == 3 and x.dtype in (torch.float32, torch.bfloat16)
+                and x.shape[0] > 0 and x.shape[2] >= 2 and x.shape[3] >= 2 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0
+                and self.conv0.weight.dtype == torch.bfloat16 and self.w_fwd.dtype == torch.bfloat16
+                and self.w_fwd.device == x.device and self.w_bwd.device == x.device and self.scale.device == x.device
+                and self.shift.device == x.device)
+
+    def forward(self, x):
+        children = list(self.children())
+        if self._covers(x):
+            x = ops.resnet_stem(x, self.w_fwd, self.w_bwd, self.scale, self.shift, self.mean, self.inv_std)
+            children = children[4:]
+        else:
+            mean = self.norm_mean.reshape(1, -1, 1, 1).to(x.dtype)      # `Normalize.forward`, operation for operation
+            std = self.norm_std.reshape(1, -1, 1, 1).to(x.dtype)
+            x = (x - mean) / std
+        for m in children:
+            x = m(x)
+        return x
+
+
+def use_own_dense_stem_(net: nn.Module, mean, std) -> int:
+    """Replace `features` of a DenseNet by an `_OwnDenseStem`, which also takes over the normalisation: the caller must no
+    longer put a `Normalize` in front of the network.  Returns how many stems were rewritten (1)."""
+    if not isinstance(net, DenseNet) or not _is_dense_stem(net.features):
+        raise ValueError("own_dense_stem rewrites the conv0 / norm0 / relu0 / pool0 stem of a DenseNet (conv 3 -> 64, 7x7, "
+                         "stride 2, pad 3; MaxPool2d(3, 2, 1))")
+    net.features = _OwnDenseStem(net.features, mean, std)
+    return 1
+
+
 class _Fp32Head(_KeepsFp32):
     """Global average pool + the last linear layer in fp32, whatever dtype the network is cast to: the weights keep their
     fp32 bits (`_KeepsFp32`), the pooled features are widened before the layer, the logits come out fp32.
@@ -1384,7 +1476,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      fuse_stem: bool = False, head_fp32=False, own_strided_conv: bool = False,
                      own_depthwise: bool = False, own_pointwise: bool = False,
                      own_first_conv: bool = False, own_dense_pointwise: bool = False,
-                     own_dense_conv: bool = False, own_dense_block: bool = False) -> nn.Module:
+                     own_dense_conv: bool = False, own_dense_block: bool = False,
+                     own_dense_transition: bool = False, own_dense_stem: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
@@ -1408,7 +1501,11 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     conditions) runs each of the 4 dense blocks on one channels_last feature buffer: the 3x3 kernels write their 32
     channels straight into it, the 1x1 kernels read a prefix of it in place, and the input gradients are accumulated in
     one gradient buffer inside the 1x1 gradient kernel (`_OwnDenseBlock`, `ops.dense_block`; no torch.cat and no
-    gradient-sum kernels inside a block; off by default)."""
+    gradient-sum kernels inside a block; off by default); own_dense_transition (needs own_dense_pointwise, independent of
+    the other two) runs each of the 3 transitions as one kernel that pools in front of the 1x1 convolution
+    (`use_own_dense_transition_`, `ops.dense_transition`; off by default); own_dense_stem (DenseNet-121, bf16,
+    channels_last, independent of the others) moves the normalisation and conv0 / norm0 / relu0 / pool0 into the stem
+    kernels (`_OwnDenseStem`; the Sequential then holds the network alone, as with fuse_stem; off by default)."""
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
@@ -1452,6 +1549,17 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     if own_dense_block and not (own_dense_pointwise and own_dense_conv):
         raise ValueError("own_dense_block needs own_dense_pointwise=True and own_dense_conv=True (the block buffer is read "
                          "and written by their kernels)")
+    if own_dense_transition and key != 'densenet121':
+        raise ValueError("own_dense_transition is a switch of DenseNet-121 (no other network has transitions)")
+    if own_dense_transition and not own_dense_pointwise:
+        raise ValueError("own_dense_transition needs own_dense_pointwise=True (it switches the transitions that switch "
+                         "rewrites)")
+    if own_dense_stem and key != 'densenet121':
+        raise ValueError("own_dense_stem is a switch of DenseNet-121 (the ResNets have fuse_stem)")
+    if own_dense_stem and dtype != torch.bfloat16:
+        raise ValueError("own_dense_stem needs a bfloat16 network (the stem kernels produce bf16 activations)")
+    if own_dense_stem and not channels_last:
+        raise ValueError("own_dense_stem needs channels_last=True (the stem kernels produce channels_last storage)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1474,6 +1582,11 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         use_own_dense_conv_(net)
     if own_dense_block:                  # after the other two: it takes over the layers they have rewritten
         use_own_dense_block_(net)
+    if own_dense_transition:             # after own_dense_pointwise: it switches the transitions that one creates
+        use_own_dense_transition_(net)
+    if own_dense_stem:                   # the module normalises: the Sequential holds the network alone
+        use_own_dense_stem_(net, mean, std)
+        stem_fused = True
     if own_head:                         # after the weights are loaded: the head keeps an fp32 copy of the Linear
         use_own_head_(net, head_fp32)
     if fuse_bn_act and isinstance(net, ResNet):

@@ -54,7 +54,7 @@ extern "C" {
  * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those, and
  * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those, and
  * adil_dense3x3_fwd / adil_dense3x3_bwd after those, and their row-pitch forms adil_dense1x1_fwd_ld / adil_dense1x1_bwd_ld /
- * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those: all additive
+ * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those: all additive
  * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls neither). */
 int adil_abi_version(void);
 
@@ -571,6 +571,35 @@ int adil_dense3x3_fwd_ld(const void* x, int ldx, const void* wp, void* y, int ld
                          int B, int H, int W, int C, int N, void* stream);
 int adil_dense3x3_bwd_ld(const void* g, int ldg, const void* wp_bwd, void* gx, int ldgx,
                          int B, int H, int W, int C, int N, void* stream);
+
+/* A transition of the frozen DenseNet-121 — eval-BatchNorm + ReLU, 1x1 convolution, AvgPool2d(2, 2) — with the pooling done
+ * IN FRONT of the convolution: the two commute, the GEMM runs on a quarter of the pixels and the full-resolution
+ * convolution output is never written.  Forward and input gradient, one kernel each way.  channels_last bf16 storage:
+ *     x, xin, gx     [B][H][W][K] bf16, dense
+ *     y              [B][H/2][W/2][N] bf16, dense
+ *     g              B H/2 W/2 pixel rows of N live elements at a row pitch of ldg ELEMENTS (the first channels of the next
+ *                    dense block's gradient buffer are read in place); columns at or behind N are never read
+ *     w              [N][K] bf16, wt [K][N] bf16 its transpose
+ *     pscale, pshift [K] fp32 : the BatchNorm in front, as for adil_dense1x1_*
+ *   Prologue : pre = fadd_rn(fmul_rn(f32(x), pscale[k]), pshift[k]), the two roundings of adil_dense1x1_* (never an fma);
+ *              p = max(pre, 0) in fp32, every pre <= 0 or NaN gives +0; p is NOT rounded to bf16.
+ *   Pooling  : output pixel (b, oh, ow) owns p00 = (2oh, 2ow), p01 = (2oh, 2ow+1), p10 = (2oh+1, 2ow), p11 = (2oh+1, 2ow+1);
+ *              s = ((p00 + p01) + p10) + p11, three fp32 adds in this order, each rounded; a = bf16_rne(s * 0.25f).
+ *   adil_dense_transition_fwd : y[b][oh][ow][n] = bf16_rne(sum_k a * w[n][k]), bf16 MFMA with fp32 accumulation in any
+ *                       order.  No table and no activation behind the convolution: a transition has none.
+ *   adil_dense_transition_bwd : t = sum_n g[mo][n] * wt[k][n] in fp32, any order, g used as stored; each of the four input
+ *                       pixels of the window gets gx = bf16_rne(fmul(fmul(t, pscale[k]), 0.25f)) where THAT pixel's own
+ *                       pre > 0, else +0; pre is recomputed from xin by the forward's two operations.  Every element of gx
+ *                       is written.  Input gradient only: the network is frozen.
+ * Limits: K % 8 == 0, N % 8 == 0, 8 <= K, N <= 2048, H and W even and >= 2, B >= 1, B H W < 2^31, ldg >= N, ldg % 8 == 0,
+ * 16-byte aligned bf16 pointers, 4-byte aligned tables.  Anything else, or a NULL pointer: ADIL_EINVAL before any launch,
+ * outputs untouched.  No load or store leaves an operand's extent: tails in K and N are clipped and zero-filled on BOTH MFMA
+ * operands, pooled pixel rows past the end read a clamped in-range row and are not stored.  Element offsets are 64-bit.
+ * One launch per call on `stream`, no allocation, no synchronisation.  No atomics: bitwise reproducible; capturable. */
+int adil_dense_transition_fwd(const void* x, const float* pscale, const float* pshift, const void* w, void* y,
+                              int B, int H, int W, int K, int N, void* stream);
+int adil_dense_transition_bwd(const void* g, int ldg, const void* wt, const void* xin, const float* pscale,
+                              const float* pshift, void* gx, int B, int H, int W, int K, int N, void* stream);
 
 #ifdef __cplusplus
 }

@@ -41,6 +41,14 @@ def build_parser():
                    help='-m densenet: 1 = each of the 4 dense blocks runs on one channels_last feature buffer (no torch.cat, '
                         'input gradients accumulated inside the 1x1 gradient kernel); needs --own-dense-pointwise 1 and '
                         '--own-dense-conv 1; 0 (default) = per-layer tensors.  Ignored otherwise')
+    p.add_argument('--own-dense-transition', type=int, default=0, choices=[0, 1],
+                   help='-m densenet: 1 = each of the 3 transitions runs as one kernel that pools in front of the 1x1 '
+                        'convolution; needs --own-dense-pointwise 1; 0 (default) = the 1x1 kernel and the library pool.  '
+                        'Ignored otherwise')
+    p.add_argument('--own-dense-stem', type=int, default=0, choices=[0, 1],
+                   help='-m densenet: 1 = a bfloat16 channels_last network whose normalisation and conv0 / norm0 / relu0 / '
+                        'pool0 run in the stem kernels; 0 (default) = the library.  Independent of the other dense switches.  '
+                        'Ignored otherwise')
     return p
 
 
@@ -54,11 +62,14 @@ def main(args):
     is_densenet = zoo.canonical_name(model_name) == 'densenet121'
     own_dense_pw, own_dense_conv = bool(args.own_dense_pointwise) and is_densenet, bool(args.own_dense_conv) and is_densenet
     own_dense_block = bool(args.own_dense_block) and is_densenet
-    own_dense = own_dense_pw or own_dense_conv or own_dense_block
+    own_dense_transition = bool(args.own_dense_transition) and is_densenet
+    own_dense_stem = bool(args.own_dense_stem) and is_densenet
+    own_dense = own_dense_pw or own_dense_conv or own_dense_block or own_dense_transition or own_dense_stem
     if own_dense:                            # the kernels work on bf16 channels_last activations
         net = zoo.build_classifier(model_name, weights=args.weights, device=device, dtype=torch.bfloat16,
                                    channels_last=True, own_dense_pointwise=own_dense_pw, own_dense_conv=own_dense_conv,
-                                   own_dense_block=own_dense_block)
+                                   own_dense_block=own_dense_block, own_dense_transition=own_dense_transition,
+                                   own_dense_stem=own_dense_stem)
         model = lambda x: net(x.to(torch.bfloat16)).float()
     else:
         net = model = zoo.build_classifier(model_name, weights=args.weights, device=device)
