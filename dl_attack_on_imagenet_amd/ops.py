@@ -974,7 +974,7 @@ def conv3x3_s2_covers(x: Tensor, cin: int, cout: int) -> bool:
     """What adil_conv3x3_s2_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
     return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == cin and cin % 64 == 0
             and cout % 64 == 0 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and 0 < x.shape[3] <= CONV3X3_S2_MAX_W
-            and x.shape[2] > 0 and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+            and x.shape[2] > 0 and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 and 9 * cin * cout < 2 ** 31)
 
 
 class Conv3x3S2Function(torch.autograd.Function):

@@ -55,7 +55,8 @@ extern "C" {
  * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those, and
  * adil_dense3x3_fwd / adil_dense3x3_bwd after those, and their row-pitch forms adil_dense1x1_fwd_ld / adil_dense1x1_bwd_ld /
  * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those: all additive
- * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls neither). */
+ * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy / adil_conv3x3_loop (test and tool entry points: the
+ * product calls none of them). */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -343,6 +344,13 @@ int adil_pw_conv_bwd_tile(const void* g, const void* g2, const void* y, const fl
                           void* gres, int M, int K, int N, int relu, const void* xin, const float* pscale,
                           const float* pshift, const void* g3, int sub_w, int sub_hw, void* stream, int bo);
 int adil_pw_route_policy(int policy);
+/* adil_conv3x3_loop sets which main loop adil_conv3x3, adil_conv3x3_s2_fwd and adil_conv3x3_s2_bwd run (a host-side int
+ * read at launch; 0 = the default: stride 1, a loop over channel chunks with its 9 taps unrolled and its LDS reads
+ * pipelined; stride 2, addresses computed once, and pipelined LDS reads on the 64-channel tile; 1 = the loops over
+ * (chunk, tap) steps they replaced, kept as the measuring baseline and the bitwise reference: both give the same bits) and
+ * returns the previous value; any other argument changes nothing and only returns the current value.  For tests and
+ * tools: the product does not call it. */
+int adil_conv3x3_loop(int variant);
 
 /* Residual join of two consecutive bottlenecks of one stage (conv3 of block i-1 and conv1 of block i) as ONE kernel;
  * the C-channel tensor between the two GEMMs is kept on chip.  W = width in {64, 128}, C = 4 W, M = pixels; bf16
@@ -365,7 +373,8 @@ int adil_pw_join_bwd(const void* g_h1, const void* h1, const float* scale1, cons
 /* 3x3 / stride 1 / pad 1 convolution of the frozen network on channels_last storage, raw bf16 output (its BatchNorm +
  * ReLU run in the next pointwise kernel's prologue):  y[B][H][W][N] = conv3x3(x[B][H][W][C]; wp), weights packed
  * wp[N][9][C] = w[n][c][kh][kw] at [n][kh*3+kw][c].  The input gradient is the same call on wp' [C][9][N] =
- * w[n][c][2-kh][2-kw] at [c][kh*3+kw][n].  C % 64 == 0, N % 64 == 0, W <= 63. */
+ * w[n][c][2-kh][2-kw] at [c][kh*3+kw][n].  C % 64 == 0, N % 64 == 0, W <= 63, and the weight pack 9 * C * N below 2^31
+ * elements (the kernel indexes it with 32 bits); anything else: ADIL_EINVAL before any launch. */
 int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream);
 
 /* 3x3 / stride 2 / pad 1 convolution of the frozen network on channels_last storage (conv2 of the first bottleneck of
@@ -378,7 +387,8 @@ int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H, int W, in
  *                         zero-upsampled), g is [B][OH][OW][N], weights wp_bwd[C][9][N] = w[n][c][kh][kw] at
  *                         [c][kh*3+kw][n] (taps NOT flipped, channels swapped).  Every element of gx is written.
  * C % 64 == 0, N % 64 == 0 (C != N allowed), H and W even, W <= ADIL_CONV3X3_S2_MAX_W (the width limit of adil_conv3x3:
- * image sizes whose stride-1 3x3 layers run here); anything else: ADIL_EINVAL before any launch, outputs untouched.
+ * image sizes whose stride-1 3x3 layers run here), 9 * C * N below 2^31 (as adil_conv3x3); anything else: ADIL_EINVAL
+ * before any launch, outputs untouched.
  * No atomics: bitwise reproducible. */
 #define ADIL_CONV3X3_S2_MAX_W 63
 int adil_conv3x3_s2_fwd(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream);
