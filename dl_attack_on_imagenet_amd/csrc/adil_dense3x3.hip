@@ -29,6 +29,7 @@
 #include "adil_common.h"
 #include "adil_hip.h"
 #include "adil_mfma.h"
+#include "adil_pw_tile.h"
 
 namespace {
 
@@ -50,21 +51,8 @@ __global__ __launch_bounds__(256) void d3_kernel(const bf16_t* __restrict__ src,
     bf16_t* sx = reinterpret_cast<bf16_t*>(smem_raw);      // [NP][D3_LS]   (later: [4][64][OS] output transpose)
     bf16_t* sw = sx + D3_NPMAX * D3_LS;                    // [9][BO][D3_LS]
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
-    // workgroups are dealt round-robin to the 8 XCDs: the OT channel tiles of one pixel tile go to ONE XCD, so the
-    // repeated reads of a halo meet in that XCD's L2.  Pixel tiles behind the last multiple of 8 keep the plain order.
     int mt, ot;
-    {
-        const int id = blockIdx.x, full = (MT >> 3) * 8 * OT;
-        if (id < full) {
-            const int xcd = id & 7, j = id >> 3;
-            ot = j % OT;
-            mt = (j / OT) * 8 + xcd;
-        } else {
-            const int r = id - full;
-            ot = r % OT;
-            mt = (MT >> 3) * 8 + r / OT;
-        }
-    }
+    pw_tile_order(MT, OT, mt, ot);                         // the OT channel tiles of one pixel tile share their halo in L2
     const long long m0 = (long long)mt * D3_BM;            // m0 + 255 may pass 2^31 - 1
     const int o0 = ot * BO;
     const int NP = D3_BM + 2 * W + 2;

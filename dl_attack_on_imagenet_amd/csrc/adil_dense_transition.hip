@@ -2,13 +2,13 @@
 // IN FRONT of the convolution (the two commute: both are linear and the 1x1 convolution is per pixel), forward and input
 // gradient: adil_dense_transition_fwd / adil_dense_transition_bwd (include/adil_hip.h).  The GEMM runs on a quarter of the
 // pixels and the full-resolution convolution output never exists.  bf16 channels_last storage, bf16 MFMA with fp32
-// accumulation, one rounding to bf16 (RNE), no atomics, 64-bit element offsets.  Siblings of d1_kernel
-// (adil_dense1x1.hip: same tiling, same MFMA roles, same tails, same XCD order), which stays as it is.
+// accumulation, one rounding to bf16 (RNE), no atomics, 64-bit element offsets.  The tile, its tails and the MFMA roles are
+// those of adil_pw_tile.h; this file has what is the two kernels' own.
 //
-// Both directions are the row-major GEMM  OUT[M][O] = A'[M][R] . B[O][R]^T  with M = B H/2 W/2 POOLED pixels.  Pooled
+// Both directions are the GEMM  OUT[M][O] = A'[M][R] . B[O][R]^T  of adil_pw_tile.h with M = B H/2 W/2 POOLED pixels.  Pooled
 // pixel mo = (b Ho + oh) Wo + ow owns the input pixels p00 = 2 (mo / Wo) W + 2 (mo % Wo), p00 + 1, p00 + W, p00 + W + 1
 // (b H W + 2 oh W = 2 W (b Ho + oh): the image index needs no division of its own).
-//   forward    A' = a = bf16(0.25 (((p00 + p01) + p10) + p11)), p = max(pre, 0) in fp32, pre = d1_pre's two roundings,
+//   forward    A' = a = bf16(0.25 (((p00 + p01) + p10) + p11)), p = max(pre, 0) in fp32, pre = pw_preact's two roundings,
 //              formed on the way from registers to LDS: the four input rows of a pooled pixel are gathered into registers
 //              together (16 x 16 bytes in flight per thread, one chunk ahead of the MFMAs);  R = K, B = w [N][K], O = N;
 //              the epilogue is the rounding alone
@@ -16,44 +16,17 @@
 //              0.25) goes through LDS ONCE per pooled pixel, and on the way out each of the four input pixels keeps v
 //              where its own pre > 0 and writes +0 elsewhere.  xin is fetched there, in the 16-byte chunks of the stores
 //              (nothing of it is held under the reduction loop), and pre is recomputed by the forward's two operations.
-//   Workgroup = 4 waves = 128 pooled pixels x BO output channels, BO = 32 CT, CT = 1 .. 5 picked as in d1_dispatch.
-//   Tails as in d1_kernel: a 16-byte chunk past R and a B row past O are read at a clamped in-range address and replaced
-//   by zeros on BOTH operands; a pooled row past M reads the window of row M - 1 and is not stored; a table entry past its
-//   extent is read at a clamped index.
+//   A pooled row past M reads the window of row M - 1 and is not stored; a table entry past its extent is read at a
+//   clamped index.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
 #include "adil_common.h"
 #include "adil_hip.h"
 #include "adil_mfma.h"
+#include "adil_pw_tile.h"
 
 namespace {
-
-#define TR_BM 128
-#define TR_BK 64
-#define TR_LS (TR_BK + 8)              // LDS row stride (elements): 144 B = 9 x 16 B
-#define TR_MAXC 2048
-
-// d1_pre (adil_dense1x1.hip): product and sum each rounded to fp32, never one fma
-__device__ __forceinline__ float tr_pre(float x, float ps, float pb) {
-#pragma clang fp contract(off)
-    const float p = x * ps;
-    return p + pb;
-}
-
-// d1_kernel's order: the OT channel tiles of one pixel tile go to ONE XCD
-__device__ __forceinline__ void tr_tile(int MT, int OT, int& mt, int& ot) {
-    const int id = blockIdx.x, full = (MT >> 3) * 8 * OT;
-    if (id < full) {
-        const int xcd = id & 7, j = id >> 3;
-        ot = j % OT;
-        mt = (j / OT) * 8 + xcd;
-    } else {
-        const int r = id - full;
-        ot = r % OT;
-        mt = (MT >> 3) * 8 + r / OT;
-    }
-}
 
 // first input pixel of the window of pooled pixel mo
 __device__ __forceinline__ size_t tr_p00(int mo, int Wo, int W) {
@@ -61,46 +34,21 @@ __device__ __forceinline__ size_t tr_p00(int mo, int Wo, int W) {
     return (size_t)2 * (size_t)r * (size_t)W + (size_t)(2 * ow);
 }
 
-// accumulators -> bf16 -> this wave's transposed buffer: lane = pixel c, quad q of tile ct = channels 32ct + 8q + 4h .. +3
-template <int CT, bool SCALED>
-__device__ __forceinline__ void tr_stage(const f32x16 (&acc)[CT], bf16_t* so, const float* otab, int c, int h) {
-    constexpr int OS = 32 * CT + 8;
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct) {
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const int co = 32 * ct + 8 * q + 4 * h;
-            float v[4];
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                v[e] = acc[ct][4 * q + e];
-                if (SCALED) v[e] = (v[e] * otab[co + e]) * 0.25f;
-            }
-            u32x2 t;
-            t[0] = pack2_bf16(v[0], v[1]);
-            t[1] = pack2_bf16(v[2], v[3]);
-            *reinterpret_cast<u32x2*>(so + c * OS + co) = t;
-        }
-    }
-}
-
 template <int CT>
 __global__ __launch_bounds__(256) void tr_fwd_kernel(const bf16_t* __restrict__ x, const float* __restrict__ pscale,
                                                      const float* __restrict__ pshift, const bf16_t* __restrict__ bm,
                                                      bf16_t* __restrict__ out, int M, int R, int O, int Wo, int W, int MT,
                                                      int OT, int tab_off) {
-    constexpr int BO = 32 * CT;
-    constexpr int ACH = TR_BM * TR_BK / 8 / 256;         // 16-byte chunks of the A tile per thread (4), each from 4 pixels
-    constexpr int OS = BO + 8;
+    constexpr int BO = 32 * CT, ACH = PW_ACH;           // each 16-byte chunk of the A tile comes from 4 pixels
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    bf16_t* sa = reinterpret_cast<bf16_t*>(smem_raw);    // [128][TR_LS]
-    bf16_t* sb = sa + TR_BM * TR_LS;                     // [BO][TR_LS]
+    bf16_t* sa = reinterpret_cast<bf16_t*>(smem_raw);    // [128][PW_LS]
+    bf16_t* sb = sa + PW_BM * PW_LS;                     // [BO][PW_LS]
     float* rtab = reinterpret_cast<float*>(smem_raw + tab_off);          // pscale | pshift, zeros behind R
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
     int mt, ot;
-    tr_tile(MT, OT, mt, ot);
-    const int m0 = mt * TR_BM, o0 = ot * BO;
-    const int nk = (R + TR_BK - 1) / TR_BK, RP = nk * TR_BK;
+    pw_tile_order(MT, OT, mt, ot);
+    const int m0 = mt * PW_BM, o0 = ot * BO;
+    const int nk = (R + PW_BK - 1) / PW_BK, RP = nk * PW_BK;
     for (int i = tid; i < RP; i += 256) {
         const bool ok = i < R;
         const int ic = ok ? i : 0;
@@ -119,10 +67,10 @@ __global__ __launch_bounds__(256) void tr_fwd_kernel(const bf16_t* __restrict__ 
     }
     u32x4 ar[ACH][4], br[CT];
     const u32x4 zero4 = {0u, 0u, 0u, 0u};
+    const PwBTile<CT> bt{br, bm, sb, o0, O, R, tid};
     auto load_tiles = [&](int kc) {
-        const int col = kc * TR_BK + (tid & 7) * 8;
-        const bool cok = col < R;
-        const int colc = cok ? col : 0;
+        bool cok;
+        const int colc = bt.column(kc, cok);
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             const bf16_t* p = x + arow[i] + colc;
@@ -135,17 +83,11 @@ __global__ __launch_bounds__(256) void tr_fwd_kernel(const bf16_t* __restrict__ 
                 for (int j = 0; j < 4; ++j) ar[i][j] = zero4;
             }
         }
-#pragma unroll
-        for (int i = 0; i < CT; ++i) {
-            const int n = o0 + ((tid + 256 * i) >> 3);
-            const bool ok = cok && n < O;
-            br[i] = *reinterpret_cast<const u32x4*>(bm + (ok ? (size_t)n * (size_t)R + colc : (size_t)0));
-            if (!ok) br[i] = zero4;
-        }
+        bt.load(cok, colc);
     };
     auto store_tiles = [&](int kc) {
         const int ch = tid & 7;
-        const float* t0 = rtab + kc * TR_BK + ch * 8;
+        const float* t0 = rtab + kc * PW_BK + ch * 8;
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             const int row = (tid + 256 * i) >> 3;
@@ -157,53 +99,31 @@ __global__ __launch_bounds__(256) void tr_fwd_kernel(const bf16_t* __restrict__ 
                 unpack8(ar[i][j], v);
 #pragma unroll
                 for (int e = 0; e < 8; ++e) {
-                    const float pre = tr_pre(v[e], t0[e], t0[RP + e]);
+                    const float pre = pw_preact(v[e], t0[e], t0[RP + e]);
                     const float p = pre > 0.0f ? pre : 0.0f;             // <= 0 (and -0.0, and NaN) -> +0
                     s[e] = j == 0 ? p : s[e] + p;                        // ((p00 + p01) + p10) + p11
                 }
             }
 #pragma unroll
             for (int e = 0; e < 8; ++e) s[e] *= 0.25f;
-            *reinterpret_cast<u32x4*>(sa + row * TR_LS + ch * 8) = pack8(s);
+            *reinterpret_cast<u32x4*>(sa + row * PW_LS + ch * 8) = pack8(s);
         }
-#pragma unroll
-        for (int i = 0; i < CT; ++i) {
-            const int row = (tid + 256 * i) >> 3;
-            *reinterpret_cast<u32x4*>(sb + row * TR_LS + ch * 8) = br[i];
-        }
+        bt.store();
     };
 
     load_tiles(0);
     f32x16 acc[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ct][r] = 0.0f;
+    pw_clear(acc);
     for (int it = 0; it < nk; ++it) {
         store_tiles(it);
         if (it + 1 < nk) load_tiles(it + 1);
         lds_barrier();
-        const bf16_t* bx = sa + (w * 32 + c) * TR_LS + 8 * h;
-        const bf16_t* bw = sb + c * TR_LS + 8 * h;
-        const int left = R - it * TR_BK;
-        const int steps = left >= TR_BK ? TR_BK / 16 : (left + 15) / 16;
-        for (int ks = 0; ks < steps; ++ks) {
-            const bf16x8 b = lds8(bx + 16 * ks);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) mma16(acc[ct], lds8(bw + ct * 32 * TR_LS + 16 * ks), b);
-        }
+        pw_mma_chunk<CT>(acc, sa, sb, R - it * PW_BK, w, c, h);
         lds_barrier();
     }
-    bf16_t* so = reinterpret_cast<bf16_t*>(smem_raw) + w * 32 * OS;     // the tile buffers are idle now
-    tr_stage<CT, false>(acc, so, nullptr, c, h);
-    constexpr int CPP = BO / 8;                          // 16-byte chunks per pixel
-#pragma unroll
-    for (int i = 0; i < 32 * CPP / 64; ++i) {
-        const int id = lane + 64 * i, px = id / CPP, ch = id - px * CPP;
-        const u32x4 t = *reinterpret_cast<const u32x4*>(so + px * OS + ch * 8);
-        const int mm = m0 + w * 32 + px, n = o0 + ch * 8;
-        if (mm < M && n < O) *reinterpret_cast<u32x4*>(out + (size_t)mm * (size_t)O + n) = t;
-    }
+    bf16_t* so = pw_stage_buffer<CT>(smem_raw, w);
+    pw_stage<CT>(acc, so, c, h, [](float (&)[4], int, int, int) {});     // the epilogue is the rounding alone
+    pw_write_out<CT>(so, out, O, m0, o0, M, O, w, lane);
 }
 
 template <int CT>
@@ -211,25 +131,23 @@ __global__ __launch_bounds__(256) void tr_bwd_kernel(const bf16_t* __restrict__ 
                                                      const bf16_t* __restrict__ xin, const float* __restrict__ pscale,
                                                      const float* __restrict__ pshift, bf16_t* __restrict__ out, int M, int R,
                                                      int O, int Wo, int W, int MT, int OT, int ldg) {
-    constexpr int BO = 32 * CT;
-    constexpr int ACH = TR_BM * TR_BK / 8 / 256;
-    constexpr int OS = BO + 8;
+    constexpr int BO = 32 * CT, ACH = PW_ACH, OS = BO + 8;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    bf16_t* sa = reinterpret_cast<bf16_t*>(smem_raw);    // [128][TR_LS]
-    bf16_t* sb = sa + TR_BM * TR_LS;                     // [BO][TR_LS]
+    bf16_t* sa = reinterpret_cast<bf16_t*>(smem_raw);    // [128][PW_LS]
+    bf16_t* sb = sa + PW_BM * PW_LS;                     // [BO][PW_LS]
     __shared__ __attribute__((aligned(16))) float otab[2 * BO];          // pscale | pshift of this channel tile
-    __shared__ int swin[TR_BM];                          // first input pixel of each pooled row's window (< 2^31)
+    __shared__ int swin[PW_BM];                          // first input pixel of each pooled row's window (< 2^31)
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
     int mt, ot;
-    tr_tile(MT, OT, mt, ot);
-    const int m0 = mt * TR_BM, o0 = ot * BO;
-    const int nk = (R + TR_BK - 1) / TR_BK;
+    pw_tile_order(MT, OT, mt, ot);
+    const int m0 = mt * PW_BM, o0 = ot * BO;
+    const int nk = (R + PW_BK - 1) / PW_BK;
     if (tid < BO) {
         const int n = o0 + tid < O ? o0 + tid : O - 1;
         otab[tid] = pscale[n];
         otab[BO + tid] = pshift[n];
     }
-    if (tid < TR_BM) swin[tid] = (int)tr_p00(m0 + tid < M ? m0 + tid : M - 1, Wo, W);
+    if (tid < PW_BM) swin[tid] = (int)tr_p00(m0 + tid < M ? m0 + tid : M - 1, Wo, W);
     __syncthreads();
 
     size_t arow[ACH];
@@ -240,61 +158,43 @@ __global__ __launch_bounds__(256) void tr_bwd_kernel(const bf16_t* __restrict__ 
     }
     u32x4 ar[ACH], br[CT];
     const u32x4 zero4 = {0u, 0u, 0u, 0u};
+    const PwBTile<CT> bt{br, bm, sb, o0, O, R, tid};
     auto load_tiles = [&](int kc) {
-        const int col = kc * TR_BK + (tid & 7) * 8;
-        const bool cok = col < R;
-        const int colc = cok ? col : 0;
+        bool cok;
+        const int colc = bt.column(kc, cok);
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             ar[i] = *reinterpret_cast<const u32x4*>(g + arow[i] + colc);
             if (!cok) ar[i] = zero4;
         }
-#pragma unroll
-        for (int i = 0; i < CT; ++i) {
-            const int n = o0 + ((tid + 256 * i) >> 3);
-            const bool ok = cok && n < O;
-            br[i] = *reinterpret_cast<const u32x4*>(bm + (ok ? (size_t)n * (size_t)R + colc : (size_t)0));
-            if (!ok) br[i] = zero4;
-        }
+        bt.load(cok, colc);
     };
-    auto store_tiles = [&]() {
+    auto store_tiles = [&](int) {
         const int ch = tid & 7;
 #pragma unroll
         for (int i = 0; i < ACH; ++i) {
             const int row = (tid + 256 * i) >> 3;
-            *reinterpret_cast<u32x4*>(sa + row * TR_LS + ch * 8) = ar[i];
+            *reinterpret_cast<u32x4*>(sa + row * PW_LS + ch * 8) = ar[i];
         }
-#pragma unroll
-        for (int i = 0; i < CT; ++i) {
-            const int row = (tid + 256 * i) >> 3;
-            *reinterpret_cast<u32x4*>(sb + row * TR_LS + ch * 8) = br[i];
-        }
+        bt.store();
     };
 
     load_tiles(0);
     f32x16 acc[CT];
-#pragma unroll
-    for (int ct = 0; ct < CT; ++ct)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[ct][r] = 0.0f;
+    pw_clear(acc);
     for (int it = 0; it < nk; ++it) {
-        store_tiles();
+        store_tiles(it);
         if (it + 1 < nk) load_tiles(it + 1);
         lds_barrier();
-        const bf16_t* bx = sa + (w * 32 + c) * TR_LS + 8 * h;
-        const bf16_t* bw = sb + c * TR_LS + 8 * h;
-        const int left = R - it * TR_BK;
-        const int steps = left >= TR_BK ? TR_BK / 16 : (left + 15) / 16;
-        for (int ks = 0; ks < steps; ++ks) {
-            const bf16x8 b = lds8(bx + 16 * ks);
-#pragma unroll
-            for (int ct = 0; ct < CT; ++ct) mma16(acc[ct], lds8(bw + ct * 32 * TR_LS + 16 * ks), b);
-        }
+        pw_mma_chunk<CT>(acc, sa, sb, R - it * PW_BK, w, c, h);
         lds_barrier();
     }
     // v = bf16((t pscale[k]) 0.25) once per pooled pixel; the four input pixels differ in their masks alone
-    bf16_t* so = reinterpret_cast<bf16_t*>(smem_raw) + w * 32 * OS;     // the tile buffers are idle now
-    tr_stage<CT, true>(acc, so, otab, c, h);
+    bf16_t* so = pw_stage_buffer<CT>(smem_raw, w);
+    pw_stage<CT>(acc, so, c, h, [&](float (&v)[4], int, int, int co) {
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[e] = (v[e] * otab[co + e]) * 0.25f;
+    });
     constexpr int CPP = BO / 8;                          // 16-byte chunks per pixel
     const size_t d01 = (size_t)O, d10 = (size_t)W * (size_t)O;
 #pragma unroll 2
@@ -325,8 +225,8 @@ __global__ __launch_bounds__(256) void tr_bwd_kernel(const bf16_t* __restrict__ 
             o4[j] = t;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
-                const unsigned lo = tr_pre(xv[2 * k], ps[2 * k], pb[2 * k]) > 0.0f ? 0x0000ffffu : 0u;
-                const unsigned hi = tr_pre(xv[2 * k + 1], ps[2 * k + 1], pb[2 * k + 1]) > 0.0f ? 0xffff0000u : 0u;
+                const unsigned lo = pw_preact(xv[2 * k], ps[2 * k], pb[2 * k]) > 0.0f ? 0x0000ffffu : 0u;
+                const unsigned hi = pw_preact(xv[2 * k + 1], ps[2 * k + 1], pb[2 * k + 1]) > 0.0f ? 0xffff0000u : 0u;
                 o4[j][k] &= lo | hi;                     // the forward's branch; elsewhere +0
             }
         }
@@ -340,37 +240,10 @@ __global__ __launch_bounds__(256) void tr_bwd_kernel(const bf16_t* __restrict__ 
     }
 }
 
+// the pooled GEMM has M = B H/2 W/2 rows
 inline bool tr_dims_ok(int B, int H, int W, int K, int N) {
-    return B >= 1 && H >= 2 && W >= 2 && (H % 2) == 0 && (W % 2) == 0 && K >= 8 && N >= 8 && K <= TR_MAXC && N <= TR_MAXC &&
-           (K % 8) == 0 && (N % 8) == 0 && (long long)B * H * W < (1ll << 31);
-}
-
-template <int CT>
-constexpr size_t tr_tile_bytes() {
-    constexpr int BO = 32 * CT;
-    constexpr size_t tiles = (size_t)(TR_BM + BO) * TR_LS * sizeof(bf16_t), trans = (size_t)4 * 32 * (BO + 8) * sizeof(bf16_t);
-    return tiles > trans ? tiles : trans;                // a multiple of 16 either way
-}
-
-template <int CT>
-void tr_launch_fwd(const bf16_t* x, const float* ps, const float* pb, const bf16_t* w, bf16_t* y, int M, int K, int N, int Wo,
-                   int W, int OT, hipStream_t s) {
-    constexpr size_t tab_off = tr_tile_bytes<CT>();
-    // widest case (CT = 5, K = 2048): 43008 B of transposed output + 16384 B of tables
-    static_assert(tab_off % 16 == 0 && tab_off + 2 * TR_MAXC * sizeof(float) <= 65536, "tiles + tables must fit 64 KiB of LDS");
-    const int MT = (M + TR_BM - 1) / TR_BM, RP = (K + TR_BK - 1) / TR_BK * TR_BK;
-    hipLaunchKernelGGL((tr_fwd_kernel<CT>), dim3((unsigned)MT * (unsigned)OT), dim3(256), tab_off + (size_t)2 * RP * sizeof(float),
-                       s, x, ps, pb, w, y, M, K, N, Wo, W, MT, OT, (int)tab_off);
-}
-
-template <int CT>
-void tr_launch_bwd(const bf16_t* g, int ldg, const bf16_t* wt, const bf16_t* xin, const float* ps, const float* pb, bf16_t* gx,
-                   int M, int K, int N, int Wo, int W, int OT, hipStream_t s) {
-    constexpr size_t bytes = tr_tile_bytes<CT>();
-    static_assert(bytes + 2 * 32 * CT * sizeof(float) + TR_BM * sizeof(int) <= 65536, "tiles + otab + swin must fit 64 KiB of LDS");
-    const int MT = (M + TR_BM - 1) / TR_BM;
-    hipLaunchKernelGGL((tr_bwd_kernel<CT>), dim3((unsigned)MT * (unsigned)OT), dim3(256), bytes, s, g, wt, xin, ps, pb, gx, M, N,
-                       K, Wo, W, MT, OT, ldg);
+    return B >= 1 && H >= 2 && W >= 2 && (H % 2) == 0 && (W % 2) == 0 && (long long)B * H * W < (1ll << 31) &&
+           pw_dims_ok(B * (H / 2) * (W / 2), K, N, 0);
 }
 
 }  // namespace
@@ -382,18 +255,19 @@ extern "C" int adil_dense_transition_fwd(const void* x, const float* pscale, con
     if (!aligned(x, 16) || !aligned(w, 16) || !aligned(y, 16) || !aligned(pscale, 4) || !aligned(pshift, 4)) return ADIL_EINVAL;
     ADIL_ENTER();
     const int Wo = W / 2, M = B * (H / 2) * Wo;
-    // fewest channel tiles of at most 160 channels that cover N, and the narrowest tile that does it (d1_dispatch)
-    const int OT = (N + 159) / 160, per = (N + OT - 1) / OT, ct = (per + 31) / 32;
     const bf16_t *xp = (const bf16_t*)x, *wp = (const bf16_t*)w;
     bf16_t* yp = (bf16_t*)y;
     hipStream_t s = (hipStream_t)stream;
-    switch (ct) {
-        case 1: tr_launch_fwd<1>(xp, pscale, pshift, wp, yp, M, K, N, Wo, W, OT, s); break;
-        case 2: tr_launch_fwd<2>(xp, pscale, pshift, wp, yp, M, K, N, Wo, W, OT, s); break;
-        case 3: tr_launch_fwd<3>(xp, pscale, pshift, wp, yp, M, K, N, Wo, W, OT, s); break;
-        case 4: tr_launch_fwd<4>(xp, pscale, pshift, wp, yp, M, K, N, Wo, W, OT, s); break;
-        default: tr_launch_fwd<5>(xp, pscale, pshift, wp, yp, M, K, N, Wo, W, OT, s); break;
-    }
+    pw_dispatch(N, [&](auto ct, int OT) {
+        constexpr int CT = decltype(ct)::value;
+        constexpr size_t tab_off = pw_tile_bytes<CT>();
+        // widest case (CT = 5, K = 2048): 43008 B of transposed output + 16384 B of tables
+        static_assert(tab_off % 16 == 0 && tab_off + 2 * PW_MAXC * sizeof(float) <= 65536, "tiles + tables must fit 64 KiB of LDS");
+        const int MT = pw_pixel_tiles(M), RP = (K + PW_BK - 1) / PW_BK * PW_BK;
+        hipLaunchKernelGGL((tr_fwd_kernel<CT>), dim3((unsigned)MT * (unsigned)OT), dim3(256),
+                           tab_off + (size_t)2 * RP * sizeof(float), s, xp, pscale, pshift, wp, yp, M, K, N, Wo, W, MT, OT,
+                           (int)tab_off);
+    });
     ADIL_CHECK_LAUNCH();
     return 0;
 }
@@ -401,23 +275,23 @@ extern "C" int adil_dense_transition_fwd(const void* x, const float* pscale, con
 extern "C" int adil_dense_transition_bwd(const void* g, int ldg, const void* wt, const void* xin, const float* pscale,
                                          const float* pshift, void* gx, int B, int H, int W, int K, int N, void* stream) {
     if (g == nullptr || wt == nullptr || xin == nullptr || pscale == nullptr || pshift == nullptr || gx == nullptr ||
-        !tr_dims_ok(B, H, W, K, N) || ldg < N || (ldg % 8) != 0)
+        !tr_dims_ok(B, H, W, K, N) || !pw_ld_ok(ldg, N))
         return ADIL_EINVAL;
     if (!aligned(g, 16) || !aligned(wt, 16) || !aligned(xin, 16) || !aligned(gx, 16) || !aligned(pscale, 4) || !aligned(pshift, 4))
         return ADIL_EINVAL;
     ADIL_ENTER();
     const int Wo = W / 2, M = B * (H / 2) * Wo;
-    const int OT = (K + 159) / 160, per = (K + OT - 1) / OT, ct = (per + 31) / 32;
     const bf16_t *gp = (const bf16_t*)g, *wp = (const bf16_t*)wt, *xp = (const bf16_t*)xin;
     bf16_t* op = (bf16_t*)gx;
     hipStream_t s = (hipStream_t)stream;
-    switch (ct) {
-        case 1: tr_launch_bwd<1>(gp, ldg, wp, xp, pscale, pshift, op, M, K, N, Wo, W, OT, s); break;
-        case 2: tr_launch_bwd<2>(gp, ldg, wp, xp, pscale, pshift, op, M, K, N, Wo, W, OT, s); break;
-        case 3: tr_launch_bwd<3>(gp, ldg, wp, xp, pscale, pshift, op, M, K, N, Wo, W, OT, s); break;
-        case 4: tr_launch_bwd<4>(gp, ldg, wp, xp, pscale, pshift, op, M, K, N, Wo, W, OT, s); break;
-        default: tr_launch_bwd<5>(gp, ldg, wp, xp, pscale, pshift, op, M, K, N, Wo, W, OT, s); break;
-    }
+    pw_dispatch(K, [&](auto ct, int OT) {
+        constexpr int CT = decltype(ct)::value;
+        constexpr size_t bytes = pw_tile_bytes<CT>();
+        static_assert(bytes + 2 * 32 * CT * sizeof(float) + PW_BM * sizeof(int) <= 65536, "tiles + otab + swin must fit 64 KiB of LDS");
+        const int MT = pw_pixel_tiles(M);
+        hipLaunchKernelGGL((tr_bwd_kernel<CT>), dim3((unsigned)MT * (unsigned)OT), dim3(256), bytes, s, gp, wp, xp, pscale, pshift,
+                           op, M, N, K, Wo, W, MT, OT, ldg);
+    });
     ADIL_CHECK_LAUNCH();
     return 0;
 }

@@ -80,10 +80,13 @@ for _k, _n, _h, _a in DENSENET_LAYERS_ALL61:
 # (M, K, N, act) of the GPU table: every shape of the network at M = 200 with its act, then the edge rows: M in {1, 127,
 # 128, 129, 300} (one pixel, around the 128-pixel tile, more than two tiles), K in {8, 24, 72, 96, 992, 2048} (no multiple
 # of 16 / of 64, one chunk and many), N in {8, 40, 128, 136, 512} (no multiple of 32, one channel tile and many); every
-# value once with act 1 and once with act 0
+# value once with act 1 and once with act 0.  The two rows at M = 1153 have ten pixel tiles and two channel tiles of 96,
+# forward (N = 192) and gradient (K = 192): eight pixel tiles are dealt round-robin to the XCDs with their channel tiles,
+# two keep the plain order
 NETWORK_ROWS = [(200, k, n, a) for k, n, _, a in DENSENET_SHAPES]
 EDGE_ROWS = [(1, 8, 8, 1), (127, 24, 40, 1), (128, 72, 128, 1), (129, 96, 136, 1), (300, 992, 512, 1), (129, 2048, 8, 1),
-             (300, 8, 512, 0), (129, 24, 136, 0), (128, 2048, 128, 0), (127, 992, 40, 0), (1, 72, 8, 0), (300, 96, 40, 0)]
+             (300, 8, 512, 0), (129, 24, 136, 0), (128, 2048, 128, 0), (127, 992, 40, 0), (1, 72, 8, 0), (300, 96, 40, 0),
+             (1153, 24, 192, 1), (1153, 192, 24, 0)]
 ROWS = NETWORK_ROWS + EDGE_ROWS
 NAN_ROWS = [(129, 24, 40), (300, 200, 136)]
 

@@ -34,6 +34,8 @@ EDGE_ROWS = [
     (1, 257, 1, 32, 32),         # one pixel more than a 256-pixel tile
     (1, 15, 17, 32, 32),         # 255 pixels: tile - 1
     (1, 16, 16, 32, 32),         # 256 pixels: the tile
+    (1, 33, 63, 32, 96),         # 2079 pixels = nine pixel tiles, eight of them dealt round-robin to the XCDs with their
+    (1, 33, 63, 96, 32),         # three channel tiles of 32, forward (N = 96) and gradient (C = 96)
 ]
 ROWS = NETWORK_ROWS + EDGE_ROWS
 NAN_ROWS = [(3, 6, 10, 64, 32), (1, 3, 63, 32, 64)]

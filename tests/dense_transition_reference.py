@@ -57,9 +57,11 @@ QUANTUM = 0.125
 # (B, H, W, K, N): one pooled pixel; pooled rows of 3 (the window must follow W, not the linear pixel index); image
 # boundaries inside a tile with K a multiple of neither 16 nor 64 and N no multiple of 32; exactly one 128-pixel pooled
 # tile; a tile tail at the network's first transition width; two channel tiles; 16 reduction chunks and four channel tiles;
-# the widest K; five images of one pooled pixel with four gradient channel tiles
+# the widest K; five images of one pooled pixel with four gradient channel tiles; 1156 pooled pixels (ten pixel tiles: eight
+# dealt round-robin to the XCDs, two in plain order) with two channel tiles of 96, forward (N = 192) and gradient (K = 192)
 ROWS = [(1, 2, 2, 8, 8), (1, 2, 6, 24, 40), (3, 4, 6, 72, 136), (2, 16, 16, 96, 128), (2, 16, 18, 256, 128),
-        (1, 14, 14, 512, 256), (1, 6, 6, 1024, 512), (1, 2, 2, 2048, 8), (5, 2, 2, 8, 512)]
+        (1, 14, 14, 512, 256), (1, 6, 6, 1024, 512), (1, 2, 2, 2048, 8), (5, 2, 2, 8, 512),
+        (1, 68, 68, 24, 192), (1, 68, 68, 192, 24)]
 # the exact leg of each row: the two sets alternate down the table
 EXACT_LEG = {row: ("clamp", "rounding")[i % 2] for i, row in enumerate(ROWS)}
 NEW_SYMBOLS = {"adil_dense_transition_fwd": 11, "adil_dense_transition_bwd": 13}

@@ -62,12 +62,15 @@ for _k, _n, _h, _a, _r in MOBILENET_LAYERS_ALL34:
 # (M, K, N, act, res) of the GPU table: the 19 (K, N) pairs at M = 200 with act / res as the network uses them, then the
 # edge rows: M in {1, 127, 128, 129, 300} (one pixel, around the 128-pixel tile, more than two tiles), K in {8, 24, 72,
 # 200, 2048} (no multiple of 16 / of 64, one chunk and many), N in {8, 24, 40, 136, 2048} (no multiple of 32, one channel
-# tile and many); every value once with act 0 and once with act 1, two rows with res
+# tile and many); every value once with act 0 and once with act 1, two rows with res.  The two rows at M = 1153 have ten
+# pixel tiles and two channel tiles of 96, forward (N = 192) and gradient (K = 192): eight pixel tiles are dealt round-robin
+# to the XCDs with their channel tiles, two keep the plain order
 NETWORK_ROWS = [(200, k, n, a, r) for k, n, _, a, r in MOBILENET_SHAPES]
 EDGE_ROWS = [(1, 8, 8, 1, False), (127, 24, 24, 1, False), (128, 72, 40, 1, False), (129, 200, 136, 1, False),
              (300, 2048, 2048, 1, False),
              (300, 8, 2048, 0, False), (129, 24, 40, 0, True), (128, 200, 24, 0, False), (127, 2048, 136, 0, True),
-             (1, 72, 8, 0, False)]
+             (1, 72, 8, 0, False),
+             (1153, 24, 192, 1, False), (1153, 192, 24, 0, False)]
 ROWS = NETWORK_ROWS + EDGE_ROWS
 NAN_ROWS = [(129, 24, 40), (300, 200, 136)]
 

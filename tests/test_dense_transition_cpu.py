@@ -80,7 +80,7 @@ def test_emulation_passes_every_row(row):
 
 
 def test_table_and_legs():
-    assert len(tr.ROWS) == 9 and len(set(tr.ROWS)) == 9
+    assert len(tr.ROWS) == 11 and len(set(tr.ROWS)) == 11
     assert sorted(set(tr.EXACT_LEG.values())) == ["clamp", "rounding"]
     for h, k, n in tr.NETWORK_TRANSITIONS:
         assert k == 2 * n and h % 2 == 0
