@@ -92,6 +92,12 @@ def build_parser():
                    help='-m densenet --dtype bf16: 1 = the normalisation and conv0 / norm0 / relu0 / pool0 run in the stem '
                         'kernels on the attack\'s own tensors; 0 (default) = the library.  Independent of the other dense '
                         'switches; with all five no library convolution or pooling is left in the trunk.  Ignored otherwise')
+    p.add_argument('--own-dense-head', default='0', choices=['0', 'inference', 'always'],
+                   help='-m densenet --dtype bf16: norm5 + ReLU + global pooling + classifier in the pooled-head kernels with '
+                        'a BatchNorm + ReLU prologue and fp32 logits on channels_last storage; inference = only inside the '
+                        'DDrague inference loop (engine.precise_head), always = in every classifier call; 0 (default) = the '
+                        'library BatchNorm, ReLU, pooling and bf16 linear layer.  Independent of the other dense switches; '
+                        'with all six no library call is left in the classifier.  Ignored otherwise')
     p.add_argument('--own-first-conv', type=int, default=0, choices=[0, 1],
                    help='-m mobilenet --dtype bf16: 1 = the normalisation and the 3 -> 32 first convolution (with its BatchNorm '
                         'and ReLU6) run in the first-convolution kernels on the attack\'s own tensors; 0 (default) = the '
@@ -176,9 +182,12 @@ def main(args):
                             and zoo.canonical_name(model_name) == 'densenet121')
     own_dense_stem = (bool(args.own_dense_stem) and dtype == torch.bfloat16
                       and zoo.canonical_name(model_name) == 'densenet121')
+    own_dense_head = ({'0': False, 'inference': 'inference', 'always': True}[args.own_dense_head]
+                      if dtype == torch.bfloat16 and zoo.canonical_name(model_name) == 'densenet121' else False)
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
                                  channels_last=(fast or own_dw or own_pw or own_fc or bool(own_head) or own_dense
-                                                or own_dense_conv or own_dense_stem),
+                                                or own_dense_conv or own_dense_stem or bool(own_dense_head)),
+                                 own_dense_head=own_dense_head,
                                  own_dense_transition=own_dense_transition, own_dense_stem=own_dense_stem,
                                  own_depthwise=own_dw, own_pointwise=own_pw, own_dense_pointwise=own_dense,
                                  own_dense_conv=own_dense_conv, own_dense_block=own_dense_block,

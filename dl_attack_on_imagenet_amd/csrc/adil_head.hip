@@ -19,6 +19,10 @@
 //                       LDS with the next step's global loads in flight during the FMAs.  16-byte loads / stores where K
 //                       resp. N is a multiple of 4, element-wise ones otherwise (any number of classes is correct, the
 //                       multiples of 4 are fast).
+//   head_bn_pool_kernel / head_bn_spread_kernel   the two stream passes behind an eval-BatchNorm + ReLU (DenseNet-121's norm5):
+//                       adil_bn_pool_head_fwd / adil_bn_pool_head_bwd.  The same decomposition; a lane loads its 8 pscale /
+//                       pshift values once, the forward sums the un-rounded max(pw_preact(x), 0), the gradient reads x once
+//                       more, recomputes the branch and masks the packed bf16 words of its value.
 // Nothing outside an operand's extents is loaded: every tail (images, channel chunks, pixels, K, N) is predicated.
 // Offsets are 64-bit; no atomics: the summation order is fixed by the decomposition, so results are reproducible.
 #include <hip/hip_runtime.h>
@@ -27,6 +31,7 @@
 #include "adil_common.h"
 #include "adil_hip.h"
 #include "adil_mfma.h"
+#include "adil_pw_tile.h"
 
 namespace {
 
@@ -92,8 +97,116 @@ __global__ __launch_bounds__(256) void head_spread_kernel(const float* __restric
     for (int hw = r; hw < HW; hw += PH_R) *reinterpret_cast<u32x4*>(p + (size_t)hw * (size_t)C) = t;
 }
 
+// ---- the same two passes behind an eval-BatchNorm + ReLU (DenseNet's norm5): adil_bn_pool_head_fwd / _bwd.  Kernels of
+// their own, so the plain pair above keeps its code and its bits.
+
+// a lane's 8 entries of a [C] fp32 table
+__device__ __forceinline__ void head_table8(const float* __restrict__ t, int c, float (&f)[8]) {
+    const f32x4 lo = *reinterpret_cast<const f32x4*>(t + c), hi = *reinterpret_cast<const f32x4*>(t + c + 4);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        f[e] = lo[e];
+        f[4 + e] = hi[e];
+    }
+}
+
+// acc += max(pre, 0) on the 8 channels of one pixel; pre <= 0 (and -0.0, and NaN) adds +0.  Nothing is rounded to bf16
+__device__ __forceinline__ void head_bn_relu_add(const u32x4& t, const float (&ps)[8], const float (&pb)[8], float (&acc)[8]) {
+    float f[8];
+    unpack8(t, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+        const float pre = pw_preact(f[e], ps[e], pb[e]);
+        acc[e] += pre > 0.0f ? pre : 0.0f;
+    }
+}
+
+// head_pool_kernel with p = max(pw_preact(x, pscale, pshift), 0) in place of x: same decomposition, same summation order
+__global__ __launch_bounds__(256) void head_bn_pool_kernel(const bf16_t* __restrict__ x, const float* __restrict__ pscale,
+                                                           const float* __restrict__ pshift, float* __restrict__ pooled,
+                                                           int HW, int C, float inv_hw) {
+    __shared__ __attribute__((aligned(16))) float part[PH_R][PH_CH];
+    const int tid = threadIdx.x, cl = tid & (PH_CL - 1), r = tid >> 5;
+    const int b = blockIdx.y, c = (blockIdx.x * PH_CL + cl) * 8;
+    float acc[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) acc[e] = 0.0f;
+    if (c < C) {
+        float ps[8], pb[8];
+        head_table8(pscale, c, ps);
+        head_table8(pshift, c, pb);
+        const bf16_t* p = x + (size_t)b * (size_t)HW * (size_t)C + (size_t)c;
+        int hw = r;
+        for (; hw + 3 * PH_R < HW; hw += 4 * PH_R) {
+            u32x4 t[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) t[j] = *reinterpret_cast<const u32x4*>(p + (size_t)(hw + j * PH_R) * (size_t)C);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) head_bn_relu_add(t[j], ps, pb, acc);
+        }
+        for (; hw < HW; hw += PH_R) head_bn_relu_add(*reinterpret_cast<const u32x4*>(p + (size_t)hw * (size_t)C), ps, pb, acc);
+    }
+    *reinterpret_cast<f32x4*>(&part[r][cl * 8]) = f32x4{acc[0], acc[1], acc[2], acc[3]};
+    *reinterpret_cast<f32x4*>(&part[r][cl * 8 + 4]) = f32x4{acc[4], acc[5], acc[6], acc[7]};
+    lds_sync();
+    const int co = blockIdx.x * PH_CH + tid;
+    if (co < C) {
+        float s = part[0][tid];
+#pragma unroll
+        for (int q = 1; q < PH_R; ++q) s += part[q][tid];
+        pooled[(size_t)b * (size_t)C + (size_t)co] = s * inv_hw;
+    }
+}
+
+// v masked by the forward's branch of one pixel: the packed bf16 words are AND-ed, as in tr_bwd_kernel's epilogue
+__device__ __forceinline__ u32x4 head_bn_mask(const u32x4& xr, const u32x4& v, const float (&ps)[8], const float (&pb)[8]) {
+    float f[8];
+    unpack8(xr, f);
+    u32x4 o = v;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const unsigned lo = pw_preact(f[2 * k], ps[2 * k], pb[2 * k]) > 0.0f ? 0x0000ffffu : 0u;
+        const unsigned hi = pw_preact(f[2 * k + 1], ps[2 * k + 1], pb[2 * k + 1]) > 0.0f ? 0xffff0000u : 0u;
+        o[k] &= lo | hi;
+    }
+    return o;
+}
+
+// head_spread_kernel behind the BatchNorm + ReLU: v = bf16((gpooled inv_hw) pscale) once per lane, then x is read once and
+// gx written once, v where that pixel's pre > 0 and +0 elsewhere
+__global__ __launch_bounds__(256) void head_bn_spread_kernel(const float* __restrict__ gpooled, const bf16_t* __restrict__ x,
+                                                             const float* __restrict__ pscale, const float* __restrict__ pshift,
+                                                             bf16_t* __restrict__ gx, int HW, int C, float inv_hw) {
+    const int tid = threadIdx.x, cl = tid & (PH_CL - 1), r = tid >> 5;
+    const int b = blockIdx.y, c = (blockIdx.x * PH_CL + cl) * 8;
+    if (c >= C) return;
+    float ps[8], pb[8], f[8];
+    head_table8(pscale, c, ps);
+    head_table8(pshift, c, pb);
+    head_table8(gpooled + (size_t)b * (size_t)C, c, f);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) f[e] = (f[e] * inv_hw) * ps[e];          // two products, each rounded, in this order
+    const u32x4 v = pack8(f);
+    const size_t base = (size_t)b * (size_t)HW * (size_t)C + (size_t)c;
+    const bf16_t* p = x + base;
+    bf16_t* q = gx + base;
+    int hw = r;
+    for (; hw + 3 * PH_R < HW; hw += 4 * PH_R) {
+        u32x4 t[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) t[j] = *reinterpret_cast<const u32x4*>(p + (size_t)(hw + j * PH_R) * (size_t)C);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            *reinterpret_cast<u32x4*>(q + (size_t)(hw + j * PH_R) * (size_t)C) = head_bn_mask(t[j], v, ps, pb);
+    }
+    for (; hw < HW; hw += PH_R) {
+        const size_t o = (size_t)hw * (size_t)C;
+        *reinterpret_cast<u32x4*>(q + o) = head_bn_mask(*reinterpret_cast<const u32x4*>(p + o), v, ps, pb);
+    }
+}
+
 // =========================================================================================================== //
-#define HG_T 64                        // output tile edge (rows and columns)
+#define HG_T 64                       // output tile edge (rows and columns)
 #define HG_K 16                        // K step
 #define HG_AS (HG_T + 4)               // row stride of the transposed a tile (floats): 272 B = 17 x 16 B
 
@@ -230,6 +343,41 @@ extern "C" int adil_pool_head_bwd(const float* g, const float* w, float* gpooled
     ADIL_CHECK_LAUNCH();
     const dim3 grid((C + PH_CH - 1) / PH_CH, B), block(256);
     hipLaunchKernelGGL(head_spread_kernel, grid, block, 0, st, (const float*)gpooled, (bf16_t*)gx, HW, C, inv_hw);
+    ADIL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int adil_bn_pool_head_fwd(const void* x, const float* pscale, const float* pshift, const float* wt, const float* bias,
+                                     float* pooled, float* logits, int B, int HW, int C, int N, void* stream) {
+    if (!x || !pscale || !pshift || !wt || !bias || !pooled || !logits || !head_args_ok(B, HW, C, N)) return ADIL_EINVAL;
+    if (!aligned(x, 16) || !aligned(pscale, 16) || !aligned(pshift, 16) || !aligned(wt, 16) || !aligned(bias, 4) ||
+        !aligned(pooled, 16) || !aligned(logits, 16))
+        return ADIL_EINVAL;
+    ADIL_ENTER();
+    hipStream_t st = (hipStream_t)stream;
+    const float inv_hw = 1.0f / (float)HW;
+    const dim3 grid((C + PH_CH - 1) / PH_CH, B), block(256);
+    hipLaunchKernelGGL(head_bn_pool_kernel, grid, block, 0, st, (const bf16_t*)x, pscale, pshift, pooled, HW, C, inv_hw);
+    ADIL_CHECK_LAUNCH();
+    head_gemm(pooled, wt, bias, logits, B, C, N, st);
+    ADIL_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int adil_bn_pool_head_bwd(const float* g, const float* w, const void* x, const float* pscale, const float* pshift,
+                                     float* gpooled, void* gx, int B, int HW, int C, int N, void* stream) {
+    if (!g || !w || !x || !pscale || !pshift || !gpooled || !gx || !head_args_ok(B, HW, C, N)) return ADIL_EINVAL;
+    if (!aligned(g, 16) || !aligned(w, 16) || !aligned(x, 16) || !aligned(pscale, 16) || !aligned(pshift, 16) ||
+        !aligned(gpooled, 16) || !aligned(gx, 16))
+        return ADIL_EINVAL;
+    ADIL_ENTER();
+    hipStream_t st = (hipStream_t)stream;
+    const float inv_hw = 1.0f / (float)HW;
+    head_gemm(g, w, nullptr, gpooled, B, N, C, st);
+    ADIL_CHECK_LAUNCH();
+    const dim3 grid((C + PH_CH - 1) / PH_CH, B), block(256);
+    hipLaunchKernelGGL(head_bn_spread_kernel, grid, block, 0, st, (const float*)gpooled, (const bf16_t*)x, pscale, pshift,
+                       (bf16_t*)gx, HW, C, inv_hw);
     ADIL_CHECK_LAUNCH();
     return 0;
 }

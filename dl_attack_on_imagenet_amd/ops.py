@@ -1668,6 +1668,64 @@ def pool_head(x: Tensor, w: Tensor, wt: Tensor, bias: Tensor) -> Tensor:
     return PoolHeadFunction.apply(x, w, wt, bias)
 
 
+def bn_pool_head_covers(x: Tensor, C: int) -> bool:
+    """What adil_bn_pool_head_fwd / _bwd accept: `pool_head_covers`'s conditions."""
+    return pool_head_covers(x, C)
+
+
+class BnPoolHeadFunction(torch.autograd.Function):
+    """`PoolHeadFunction` behind an eval-BatchNorm + ReLU given as the fp32 tables pscale / pshift
+    (adil_bn_pool_head_fwd: one pass over x, one fp32 GEMM; adil_bn_pool_head_bwd: the fp32 GEMM against the weight and
+    one pass that reads x again and writes the masked bf16 gradient).  The forward saves x and the tables, no mask.  The
+    pooled features, their gradient and gx come from the torch allocator (the call is capturable).  No weight gradient:
+    the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, pscale, pshift, w, wt, bias):
+        lib = _lib.load()
+        b, c, h, wd = x.shape
+        n = w.shape[0]
+        x2 = _nhwc(x)
+        pooled = torch.empty((b, c), dtype=torch.float32, device=x.device)
+        logits = torch.empty((b, n), dtype=torch.float32, device=x.device)
+        if b > 0:
+            _lib.check(lib.adil_bn_pool_head_fwd(_ptr(x2), _ptr(pscale), _ptr(pshift), _ptr(wt), _ptr(bias), _ptr(pooled),
+                                                 _ptr(logits), b, h * wd, c, n, _stream()), "adil_bn_pool_head_fwd")
+        ctx.save_for_backward(x2, pscale, pshift, w)
+        ctx.meta = (b, c, h, wd)
+        return logits
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        x2, pscale, pshift, w = ctx.saved_tensors
+        b, c, h, wd = ctx.meta
+        n = w.shape[0]
+        if g.dtype != torch.float32 or tuple(g.shape) != (b, n):
+            raise ValueError(f"the logit gradient must be a float32 {(b, n)} tensor, got {g.dtype} {tuple(g.shape)}")
+        g2 = g if g.is_contiguous() else g.contiguous()
+        gpooled = torch.empty((b, c), dtype=torch.float32, device=g2.device)
+        gx = torch.empty((b, h, wd, c), dtype=torch.bfloat16, device=g2.device)
+        if b > 0:
+            _lib.check(lib.adil_bn_pool_head_bwd(_ptr(g2), _ptr(w), _ptr(x2), _ptr(pscale), _ptr(pshift), _ptr(gpooled),
+                                                 _ptr(gx), b, h * wd, c, n, _stream()), "adil_bn_pool_head_bwd")
+        return gx.permute(0, 3, 1, 2), None, None, None, None, None
+
+
+def bn_pool_head(x: Tensor, pscale: Tensor, pshift: Tensor, w: Tensor, wt: Tensor, bias: Tensor) -> Tensor:
+    """x (B,C,H,W) bf16 in channels_last memory format -> mean over (H,W) of max(x * pscale + pshift, 0), . w^T + bias as
+    fp32 (B,N) logits, no copy of x.  pscale, pshift (C,), w (N,C), its transpose wt (C,N) and bias (N,) are fp32."""
+    if w.dim() != 2:
+        raise ValueError(f"w must be a (N, C) matrix, got {tuple(w.shape)}")
+    n, c = w.shape
+    if not bn_pool_head_covers(x, c) or not 1 <= n <= POOL_HEAD_MAX_CLASSES:
+        raise ValueError(f"adil_bn_pool_head does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with a {n} x "
+                         f"{c} weight (bf16, channels_last)")
+    _check_operands(x.device, ("pscale", pscale, (c,), torch.float32), ("pshift", pshift, (c,), torch.float32),
+                    ("w", w, (n, c), torch.float32), ("wt", wt, (c, n), torch.float32), ("bias", bias, (n,), torch.float32))
+    return BnPoolHeadFunction.apply(x, pscale, pshift, w, wt, bias)
+
+
 # --------------------------------------------------------------------------- #
 class DictSynthFunction(torch.autograd.Function):
     """x + D v[index] as a differentiable op (the tensordot of adil.py:25 and its autograd backward).

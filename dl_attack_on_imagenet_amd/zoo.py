@@ -161,10 +161,25 @@ class DenseNet(nn.Module):
         for m in self.modules():
             if isinstance(m, nn.Conv2d):
                 nn.init.kaiming_normal_(m.weight)
+        self.head32, self.head32_on = None, False        # an `_OwnDenseHead`, attached by use_own_dense_head_
 
     def forward(self, x):
+        if self.head32 is not None and self.head32_on:   # the trunk up to `norm5`, which the head applies itself
+            if isinstance(self.features, _OwnDenseStem):
+                return self.head32(self.features(x, skip_last=True))
+            for m in list(self.features.children())[:-1]:
+                x = m(x)
+            return self.head32(x)
         x = F.relu(self.features(x), inplace=True)
         return self.classifier(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1))
+
+    def precise_head(self, enabled: bool) -> bool:
+        """Switch the fp32 head on / off (networks rewritten by use_own_dense_head_(net, "inference")); returns the
+        previous state.  The protocol of `FusedResNet.precise_head`, which is what engine.precise_head looks for."""
+        prev = self.head32_on
+        if self.head32 is not None:
+            self.head32_on = bool(enabled)
+        return prev
 
 
 # ----------------------------------------------------------------------------- ViT-B/16
@@ -1282,8 +1297,10 @@ class _OwnDenseStem(_KeepsFp32, nn.Sequential):
                 and self.w_fwd.device == x.device and self.w_bwd.device == x.device and self.scale.device == x.device
                 and self.shift.device == x.device)
 
-    def forward(self, x):
+    def forward(self, x, skip_last: bool = False):
         children = list(self.children())
+        if skip_last:                   # `DenseNet.forward` with the own head on: `norm5` runs inside the head
+            children = children[:-1]
         if self._covers(x):
             x = ops.resnet_stem(x, self.w_fwd, self.w_bwd, self.scale, self.shift, self.mean, self.inv_std)
             children = children[4:]
@@ -1355,6 +1372,56 @@ def use_own_head_(net: nn.Module, mode=True) -> int:
     if not isinstance(net, MobileNetV2) or not isinstance(net.classifier[-1], nn.Linear):
         raise ValueError("the own head rewrites the pooling + classifier of MobileNetV2")
     net.head32 = _OwnHead(net.classifier[-1])
+    net.head32_on = mode is True
+    return 1
+
+
+class _OwnDenseHead(_Fp32Head):
+    """The end of a DenseNet, `norm5 -> ReLU -> global average pool -> classifier`, on the output of the last dense block:
+    ONE kernel pass each way (`ops.bn_pool_head`: a single read of the bf16 channels_last activation gives the fp32 pooled
+    features of the un-rounded max(norm5(x), 0), an fp32 GEMM the fp32 logits; the backward reads x once more and writes
+    the bf16 gradient once) where the kernels cover the input.  It holds the Linear's `weight` [N][C] and `bias`, the
+    transpose `wt` [C][N] and the BatchNorm as `pscale` / `pshift` (`_bn_affine`), all fp32 whatever the network is cast
+    to and all NON-persistent: `norm5` and `classifier` stay in the network under their names, so the state_dict has the
+    plain network's keys.  On every other input (CPU, fp32 activations, not channels_last) the same function is computed
+    in torch, in fp32; the logits are fp32 everywhere."""
+    _KEEP_FP32 = ('weight', 'bias', 'wt', 'pscale', 'pshift')
+
+    def __init__(self, bn: nn.BatchNorm2d, fc: nn.Linear):
+        super().__init__(fc)
+        for name in ('weight', 'bias'):                  # `_Fp32Head` registered them as persistent buffers
+            self.register_buffer(name, getattr(self, name), persistent=False)
+        self.register_buffer('wt', self.weight.t().contiguous(), persistent=False)
+        pscale, pshift = _bn_affine(bn)
+        self.register_buffer('pscale', pscale, persistent=False)
+        self.register_buffer('pshift', pshift, persistent=False)
+
+    def forward(self, x):
+        if (ops.bn_pool_head_covers(x, self.weight.shape[1])
+                and all(getattr(self, n).device == x.device for n in self._KEEP_FP32)):
+            return ops.bn_pool_head(x, self.pscale, self.pshift, self.weight, self.wt, self.bias)
+        pre = x.float() * self.pscale.reshape(1, -1, 1, 1) + self.pshift.reshape(1, -1, 1, 1)
+        return F.linear(F.relu(pre).mean(dim=(2, 3)), self.weight, self.bias)
+
+
+def _has_dense_head(net) -> bool:
+    mods = getattr(getattr(net, 'features', None), '_modules', {})
+    return (isinstance(net, DenseNet) and len(mods) > 0 and list(mods)[-1] == 'norm5'
+            and isinstance(mods['norm5'], nn.BatchNorm2d) and isinstance(net.classifier, nn.Linear)
+            and mods['norm5'].num_features == net.classifier.in_features)
+
+
+def use_own_dense_head_(net: nn.Module, mode=True) -> int:
+    """Attach an `_OwnDenseHead` built from `features.norm5` and `classifier` of a DenseNet (after its weights are loaded)
+    and route the network's forward through it: `mode` True = always, "inference" = only while `precise_head(True)` is in
+    force (engine.precise_head, the DDrague inference solver).  `norm5` and `classifier` stay in place under their names
+    and serve the network whenever the head is off.  Returns how many heads were attached (1)."""
+    if mode not in (True, "inference"):
+        raise ValueError("the own dense head's mode must be True or 'inference'")
+    if not _has_dense_head(net):
+        raise ValueError("the own dense head rewrites norm5 + ReLU + pooling + classifier of a DenseNet (features ending in "
+                         "a BatchNorm2d named norm5, a Linear classifier)")
+    net.head32 = _OwnDenseHead(net.features.norm5, net.classifier)
     net.head32_on = mode is True
     return 1
 
@@ -1477,7 +1544,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      own_depthwise: bool = False, own_pointwise: bool = False,
                      own_first_conv: bool = False, own_dense_pointwise: bool = False,
                      own_dense_conv: bool = False, own_dense_block: bool = False,
-                     own_dense_transition: bool = False, own_dense_stem: bool = False) -> nn.Module:
+                     own_dense_transition: bool = False, own_dense_stem: bool = False,
+                     own_dense_head=False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
@@ -1505,7 +1573,13 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     the other two) runs each of the 3 transitions as one kernel that pools in front of the 1x1 convolution
     (`use_own_dense_transition_`, `ops.dense_transition`; off by default); own_dense_stem (DenseNet-121, bf16,
     channels_last, independent of the others) moves the normalisation and conv0 / norm0 / relu0 / pool0 into the stem
-    kernels (`_OwnDenseStem`; the Sequential then holds the network alone, as with fuse_stem; off by default)."""
+    kernels (`_OwnDenseStem`; the Sequential then holds the network alone, as with fuse_stem; off by default);
+    own_dense_head (DenseNet-121, bf16, channels_last, independent of the other five) runs norm5 + ReLU + global pooling +
+    classifier in the pooled-head kernels with the BatchNorm + ReLU prologue and gives fp32 logits (`_OwnDenseHead`,
+    `ops.bn_pool_head`): True = in every call, "inference" = only inside engine.precise_head (the DDrague inference
+    solver; the learner keeps the library head and bf16 logits), as head_fp32 does for MobileNetV2; head_fp32 itself
+    stays a switch of the other networks; off by default.  With all six switches no library call is left in
+    DenseNet-121."""
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
@@ -1560,6 +1634,14 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         raise ValueError("own_dense_stem needs a bfloat16 network (the stem kernels produce bf16 activations)")
     if own_dense_stem and not channels_last:
         raise ValueError("own_dense_stem needs channels_last=True (the stem kernels produce channels_last storage)")
+    if own_dense_head not in (False, True, "inference"):
+        raise ValueError("own_dense_head must be False, True or 'inference'")
+    if own_dense_head and key != 'densenet121':
+        raise ValueError("own_dense_head is a switch of DenseNet-121 (MobileNetV2 and the ResNets have head_fp32)")
+    if own_dense_head and dtype != torch.bfloat16:
+        raise ValueError("own_dense_head needs a bfloat16 network (the head kernels work on bf16 activations)")
+    if own_dense_head and not channels_last:
+        raise ValueError("own_dense_head needs channels_last=True (the head kernels work on channels_last storage)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1589,6 +1671,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         stem_fused = True
     if own_head:                         # after the weights are loaded: the head keeps an fp32 copy of the Linear
         use_own_head_(net, head_fp32)
+    if own_dense_head:                   # after the weights are loaded: fp32 copies of the Linear and of norm5's affine map
+        use_own_dense_head_(net, own_dense_head)
     if fuse_bn_act and isinstance(net, ResNet):
         stem_fused = bool(fuse_stem)
         if stem_fused and dtype != torch.bfloat16:

@@ -54,7 +54,7 @@ extern "C" {
  * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those, and
  * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those, and
  * adil_dense3x3_fwd / adil_dense3x3_bwd after those, and their row-pitch forms adil_dense1x1_fwd_ld / adil_dense1x1_bwd_ld /
- * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those: all additive
+ * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those, and adil_bn_pool_head_fwd / adil_bn_pool_head_bwd after those: all additive
  * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy / adil_conv3x3_loop (test and tool entry points: the
  * product calls none of them). */
 int adil_abi_version(void);
@@ -496,6 +496,25 @@ int adil_first3x3_bwd(const void* g, const void* y, const float* scale, const vo
 int adil_pool_head_fwd(const void* x, const float* wt, const float* bias, float* pooled, float* logits, int B, int HW,
                        int C, int N, void* stream);
 int adil_pool_head_bwd(const float* g, const float* w, float* gpooled, void* gx, int B, int HW, int C, int N, void* stream);
+
+/* The same head behind an eval-BatchNorm + ReLU (DenseNet-121: norm5, ReLU, global pooling, classifier): the activation in
+ * front of the BatchNorm is read once for fp32 pooled features and fp32 logits, and read once more for the input gradient.
+ * Operands as above, and
+ *     pscale, pshift  [C] fp32 : the BatchNorm (scale = gamma / sqrt(var + eps), shift = beta - mean * scale)
+ *   pre[b][hw][c] = fadd_rn(fmul_rn(f32(x[b][hw][c]), pscale[c]), pshift[c]): the prologue of adil_dense1x1_fwd, two fp32
+ *   roundings and no contraction; p = pre > 0 ? pre : +0 (-0.0 and NaN give +0).  p is never rounded to bf16.
+ *   adil_bn_pool_head_fwd : S[b][c] = sum_hw p in fp32, in adil_pool_head_fwd's order (the pixels hw = r, r + 8, ... in
+ *                           ascending order for r = 0 .. 7, then the eight partial sums r = 0 .. 7 in ascending order);
+ *                           pooled = f32(S * inv_hw); logits as adil_pool_head_fwd.
+ *   adil_bn_pool_head_bwd : gpooled as adil_pool_head_bwd; v[b][c] = f32(f32(gpooled[b][c] * inv_hw) * pscale[c]), two fp32
+ *                           products in this order; gx[b][hw][c] = bf16_rne(v[b][c]) where pre[b][hw][c] > 0, else +0; pre is
+ *                           recomputed from x.  Every element of gx is written; gx must not overlap x.
+ * Limits, alignment (pscale and pshift 16-byte aligned too), refusals, predication, 64-bit offsets, launches and
+ * reproducibility as adil_pool_head_*. */
+int adil_bn_pool_head_fwd(const void* x, const float* pscale, const float* pshift, const float* wt, const float* bias,
+                          float* pooled, float* logits, int B, int HW, int C, int N, void* stream);
+int adil_bn_pool_head_bwd(const float* g, const float* w, const void* x, const float* pscale, const float* pshift,
+                          float* gpooled, void* gx, int B, int HW, int C, int N, void* stream);
 
 /* Pre-activated pointwise (1x1, stride 1) convolution of the frozen DenseNet-121: the eval-BatchNorm + ReLU IN FRONT of the
  * convolution (on the concatenated input of a dense layer or a transition, K = 64 .. 1024 in steps of 32) is applied on the
