@@ -152,7 +152,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
 
 // =========================================================================================================== //
 // maxpool 3x3 / stride 2 / pad 1 on NHWC bf16, 8 channels per thread; also records the argmax position
-// (kh * 3 + kw, first maximum in scan order, NaN wins — the rule of torch's max_pool2d) for the backward.
+// (kh * 3 + kw, first maximum in scan order under >, a NaN always replaces the running value so the LAST NaN of a window
+// wins — the rule of torch's max_pool2d) for the backward.  Padding taps are skipped, not read as zeros.
 // =========================================================================================================== //
 
 __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const bf16_t* __restrict__ y, bf16_t* __restrict__ p,
@@ -372,7 +373,9 @@ extern "C" int adil_stem_conv_fwd(const void* x, int x_dtype, const void* w_fwd,
                                   float inv_std0, float inv_std1, float inv_std2, const float* scale, const float* shift,
                                   void* y, int B, int H, int W, void* stream) {
     ADIL_ENTER();
-    if (!x || !w_fwd || !scale || !shift || !y || B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return ADIL_EINVAL;
+    // B is blockIdx.z: beyond 65535 images the outcome would be the runtime's (a launch error code, or a launch), so refuse
+    if (!x || !w_fwd || !scale || !shift || !y || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return ADIL_EINVAL;
+    if (x_dtype != ADIL_F32 && x_dtype != ADIL_BF16) return ADIL_EINVAL;
     const StemNorm nm = {{mean0, mean1, mean2}, {inv_std0, inv_std1, inv_std2}};
     const int OH = H / 2, OW = W / 2;
     const dim3 grid((OW + ST_T - 1) / ST_T, (OH + ST_T - 1) / ST_T, B);
@@ -380,11 +383,9 @@ extern "C" int adil_stem_conv_fwd(const void* x, int x_dtype, const void* w_fwd,
     if (x_dtype == ADIL_F32)
         hipLaunchKernelGGL(stem_conv_fwd_kernel<float>, grid, dim3(256), 0, st, (const float*)x, (const bf16_t*)w_fwd, nm,
                            scale, shift, (bf16_t*)y, H, W, OH, OW);
-    else if (x_dtype == ADIL_BF16)
+    else
         hipLaunchKernelGGL(stem_conv_fwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)x, (const bf16_t*)w_fwd, nm,
                            scale, shift, (bf16_t*)y, H, W, OH, OW);
-    else
-        return ADIL_EINVAL;
     ADIL_CHECK_LAUNCH();
     return 0;
 }
@@ -415,7 +416,8 @@ extern "C" int adil_stem_pool_bwd(const void* g, const uint8_t* idx, const void*
 extern "C" int adil_stem_conv_bwd(const void* gy, const void* w_bwd, float inv_std0, float inv_std1, float inv_std2, void* gx,
                                   int gx_dtype, int B, int H, int W, void* stream) {
     ADIL_ENTER();
-    if (!gy || !w_bwd || !gx || B <= 0 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return ADIL_EINVAL;
+    if (!gy || !w_bwd || !gx || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return ADIL_EINVAL;   // B is blockIdx.z
+    if (gx_dtype != ADIL_F32 && gx_dtype != ADIL_BF16) return ADIL_EINVAL;
     const StemNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};
     const int OH = H / 2, OW = W / 2;
     const dim3 grid((W + SB_TW - 1) / SB_TW, (H + SB_TH - 1) / SB_TH, B);
@@ -423,11 +425,9 @@ extern "C" int adil_stem_conv_bwd(const void* gy, const void* w_bwd, float inv_s
     if (gx_dtype == ADIL_F32)
         hipLaunchKernelGGL(stem_conv_bwd_kernel<float>, grid, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd, nm,
                            (float*)gx, H, W, OH, OW);
-    else if (gx_dtype == ADIL_BF16)
+    else
         hipLaunchKernelGGL(stem_conv_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd, nm,
                            (bf16_t*)gx, H, W, OH, OW);
-    else
-        return ADIL_EINVAL;
     ADIL_CHECK_LAUNCH();
     return 0;
 }

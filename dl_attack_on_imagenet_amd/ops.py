@@ -1478,6 +1478,9 @@ def pack_stem_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
     return wf.to(torch.bfloat16).reshape(64, 224).contiguous(), wb.to(torch.bfloat16).reshape(4, 49 * 64).contiguous()
 
 
+STEM_MAX_BATCH = 65535       # the image index is a grid dimension of adil_stem_conv_fwd / _bwd (include/adil_hip.h)
+
+
 class StemFunction(torch.autograd.Function):
     """Normalize -> conv7x7/2 -> BatchNorm(eval) -> ReLU -> maxpool3x3/2 of a frozen ResNet as four HIP kernels
     (csrc/adil_stem.hip), forward and input gradient.  x: (B,3,H,W) fp32/bf16 contiguous; returns the pooled
@@ -1492,6 +1495,8 @@ class StemFunction(torch.autograd.Function):
         b, _, h, w = x.shape
         if h % 2 or w % 2:
             raise ValueError("stem kernels need even H and W")
+        if b > STEM_MAX_BATCH:
+            raise ValueError(f"stem kernels take at most {STEM_MAX_BATCH} images per call, got {b}")
         oh, ow = h // 2, w // 2
         ph, pw = (oh - 1) // 2 + 1, (ow - 1) // 2 + 1
         y1 = torch.empty((b, oh, ow, 64), dtype=torch.bfloat16, device=x.device)

@@ -299,7 +299,20 @@ int adil_affine_act_bwd(const void* g, const void* y, const float* scale, void* 
  *   adil_maxpool_fwd   : p = maxpool3x3/2/pad1(y) (B x OH x OW x C -> B x PH x PW x C, PH = (OH-1)/2+1), idx = position
  *                        kh*3+kw of the first maximum (torch.nn.functional.max_pool2d's rule); C % 8 == 0
  *   adil_stem_pool_bwd : gy = route(g; idx) * [p > 0] * scale[c]   (maxpool + ReLU + BatchNorm backward, B x OH x OW x C)
- *   adil_stem_conv_bwd : gx = inv_std[ci] * conv7x7/2 input gradient of gy   (B x 3 x H x W, gx_dtype) */
+ *   adil_stem_conv_bwd : gx = inv_std[ci] * conv7x7/2 input gradient of gy   (B x 3 x H x W, gx_dtype)
+ * The two convolutions take the image index as a grid dimension: 1 <= B <= 65535.  ADIL_EINVAL, before any launch, for a
+ * NULL pointer, a non-positive size, odd H or W, B > 65535, a dtype code outside the two, or (pooling) C % 8 != 0.
+ * Arithmetic of the pooling pair (restated in tests/stem_pool_reference.py, which the kernels must equal bit for bit):
+ *   adil_maxpool_fwd   : the window of (ph, pw) is the taps (kh, kw), scanned in the order kh*3+kw, whose pixel
+ *                        (2ph-1+kh, 2pw-1+kw) lies inside the grid; padding taps are ABSENT, not zeros (a window of negative
+ *                        values has a negative maximum).  p is the first maximum under > (+0 and -0 compare equal: the
+ *                        earlier one stays, with its sign); a NaN always replaces the running value, so the LAST NaN of a
+ *                        window wins.  idx is that tap's kh*3+kw.  p is a selection: it carries the input's bit pattern
+ *                        (a NaN stays a NaN).
+ *   adil_stem_pool_bwd : per element of gy, the fp32 sum, in ascending (ph, pw) order, of the at most four g whose window
+ *                        contains the pixel, whose idx names it and whose p > 0 BY VALUE (-0, negatives and NaN fail), then
+ *                        ONE fp32 product with scale[c] and ONE rounding to bf16, to nearest even.  Every element of gy is
+ *                        written (an element no window routes to is a zero); no sign of zero is promised. */
 int adil_stem_conv_fwd(const void* x, int x_dtype, const void* w_fwd, float mean0, float mean1, float mean2, float inv_std0,
                        float inv_std1, float inv_std2, const float* scale, const float* shift, void* y, int B, int H, int W,
                        void* stream);
