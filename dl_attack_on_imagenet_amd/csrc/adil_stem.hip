@@ -366,7 +366,239 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
     }
 }
 
+// =========================================================================================================== //
+// stem_pool_bwd, quad form (adil_stem_bwd_variant 0).  The pooled grid is also the grid of 2 x 2 quads of conv-output
+// pixels (PH = ceil(OH / 2), PW = ceil(OW / 2)): one thread per (n, a, b, 8 channels) loads the four windows (a, b),
+// (a, b+1), (a+1, b), (a+1, b+1) up front — idx, g and p each, clamped and masked at the far edges, 12 loads in flight —
+// and writes the up to four pixels (2a + {0,1}, 2b + {0,1}).  Per element the sum runs over window rows, then window
+// columns, as in the gather form above; a masked window adds +0 to a sum that is never -0, which changes no bit.  A
+// pooled element is fetched by 4 threads, not 9; n and a come from blockIdx (no 64-bit division).
+// =========================================================================================================== //
+__global__ __launch_bounds__(256) void stem_pool_bwd_quad_kernel(const bf16_t* __restrict__ g, const uint8_t* __restrict__ idx,
+                                                                 const bf16_t* __restrict__ p, const float* __restrict__ scale,
+                                                                 bf16_t* __restrict__ gy, int OH, int OW, int PH, int PW,
+                                                                 int C8) {
+    const unsigned j = blockIdx.y * 256u + threadIdx.x;    // (b, c8) of this row of quads
+    if (j >= (unsigned)PW * (unsigned)C8) return;
+    const int b = (int)(j / (unsigned)C8), c8 = (int)(j - (unsigned)b * (unsigned)C8);
+    const int n = (int)(blockIdx.x / (unsigned)PH), a = (int)(blockIdx.x - (unsigned)n * (unsigned)PH);
+    const bool oka = a + 1 < PH, okb = b + 1 < PW;
+    const int a1 = oka ? a + 1 : a, b1 = okb ? b + 1 : b;
+    const size_t r0 = ((size_t)n * PH + a) * PW, r1 = ((size_t)n * PH + a1) * PW;
+    const size_t at[4] = {((r0 + b) * C8 + c8) * 8, ((r0 + b1) * C8 + c8) * 8, ((r1 + b) * C8 + c8) * 8,
+                          ((r1 + b1) * C8 + c8) * 8};
+    u32x2 id[4];
+    u32x4 gt[4], pt[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        id[k] = *reinterpret_cast<const u32x2*>(idx + at[k]);
+        gt[k] = *reinterpret_cast<const u32x4*>(g + at[k]);
+        pt[k] = *reinterpret_cast<const u32x4*>(p + at[k]);
+    }
+    const bool okw[4] = {true, okb, oka, oka && okb};
+    float sc[8];
+#pragma unroll
+    for (int jj = 0; jj < 8; ++jj) sc[jj] = scale[c8 * 8 + jj];
+    // routed[k][jj]: the gradient of window k where its argmax byte and ReLU sign admit it; the argmax byte is tested
+    // per pixel below (a window reaches up to 4 of the quad's pixels under different bytes)
+    float gf[4][8];
+    bool pos[4][8];
+    unsigned kk[4][8];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        float pf[8];
+        unpack8(gt[k], gf[k]);
+        unpack8(pt[k], pf);
+#pragma unroll
+        for (int jj = 0; jj < 8; ++jj) {
+            kk[k][jj] = (id[k][jj >> 2] >> (8 * (jj & 3))) & 0xffu;
+            pos[k][jj] = okw[k] && pf[jj] > 0.0f;
+        }
+    }
+    // pixel (2a + dy, 2b + dx): windows in the gather form's order, want = kh * 3 + kw of the pixel inside window k
+    //   (0,0): k0 @ 4          (0,1): k0 @ 5, k1 @ 3          (1,0): k0 @ 7, k2 @ 1          (1,1): k0 @ 8, k1 @ 6, k2 @ 2, k3 @ 0
+#pragma unroll
+    for (int dy = 0; dy < 2; ++dy) {
+#pragma unroll
+        for (int dx = 0; dx < 2; ++dx) {
+            const int oh = 2 * a + dy, ow = 2 * b + dx;
+            float acc[8];
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) acc[jj] = 0.0f;
+#pragma unroll
+            for (int wy = 0; wy <= dy; ++wy) {
+#pragma unroll
+                for (int wx = 0; wx <= dx; ++wx) {
+                    const int k = 2 * wy + wx;
+                    const unsigned want = (unsigned)((dy + 1 - 2 * wy) * 3 + (dx + 1 - 2 * wx));
+#pragma unroll
+                    for (int jj = 0; jj < 8; ++jj) acc[jj] += (kk[k][jj] == want && pos[k][jj]) ? gf[k][jj] : 0.0f;
+                }
+            }
+#pragma unroll
+            for (int jj = 0; jj < 8; ++jj) acc[jj] *= sc[jj];
+            if (oh < OH && ow < OW)
+                *reinterpret_cast<u32x4*>(gy + ((((size_t)n * OH + oh) * OW + ow) * C8 + c8) * 8) = pack8(acc);
+        }
+    }
+}
+
+// =========================================================================================================== //
+// stem_conv_bwd, shift form (adil_stem_bwd_variant 0).  A tap of parity class (A, BB) reads g_y1 at row shift
+// dr = (A + 3 - kh) / 2 and column shift dc = (BB + 3 - kw) / 2, both in {-1, 0, 1, 2}, and for a given (dr, dc) every
+// class has at most one tap: the 49 (class, tap) steps of the class form above are 16 shifts.  The B fragment (g_y1)
+// depends on the shift alone, so the four classes share it and ONE MFMA per (shift, channel half, sub-row):
+//   A row 4 * class + ci = w[co][ci][A + 3 - 2 dr][BB + 3 - 2 dc], zero where the class has no tap at this shift
+//   (A = 0 with dr = 2, BB = 0 with dc = 2) and for ci = 3; C register r of lane l is row 4 * (l >> 4) + r, so lane group
+//   l >> 4 ends up with class l >> 4, ci in registers 0..2, pixel column l & 15.
+// 64 MFMAs per wave instead of 196, 12 useful rows of 16 instead of 3.  Bits: walking dr = 2, 1, 0, -1 outside,
+// dc = 2, 1, 0, -1 inside, then the channel half, every class meets its own taps in the class form's order (kh, kw
+// ascending, cg) under the same instruction shape; the extra MFMAs have a zero A row and add an exact zero to a sum
+// that started at +0 and so is never -0.  That holds for every finite g_y1: a non-finite g_y1 value turns 0 * inf into
+// NaN at the pixels of the other classes under the same shift (adil_hip.h).
+// LDS: the g_y1 tile at a pixel stride of 160 B (the 16 lanes that ds_read_b128 serves together — 8 pixels of one K
+//   slice and the other 8 pixels of the next — then fall on 16 different 16-byte bank groups; at the class form's 144 B
+//   this kernel took 335 us instead of 296 at B = 512), and the three weight rows with padded kh and ci strides, so that
+//   the 12 rows x 4 K slices of an A fragment do the same.  52.7 KB: 3 workgroups per CU, as the class form.
+// Grid: the 16 x 32 tile is the class form's, but the launch is one resident set of workgroups (3 per CU) that each walk
+//   a run of consecutive tiles: the weights are staged once per workgroup, not once per tile (18.8 KB next to a 26.8 KB
+//   tile), and the global loads of tile t + 1 are issued in front of the MFMAs of tile t and written to LDS behind them
+//   (one tile per workgroup: 296 us at B = 512; this form: 246 - 262 us).
+// =========================================================================================================== //
+#define SQ_PS 80                       // g_y1 pixel stride (elements): 160 B
+#define SQ_WKH (7 * 64 + 8)            // weight stride of kh (elements): 57 x 16 B
+#define SQ_WCI (7 * SQ_WKH + 24)       // weight stride of ci (elements): 402 x 16 B
+#define SQ_WN (2 * SQ_WCI + 6 * SQ_WKH + 7 * 64)   // weight image, followed by one zero chunk
+
+template <typename TX>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void stem_conv_bwd_shift_kernel(
+    const bf16_t* __restrict__ gy, const bf16_t* __restrict__ wb, StemNorm nm, TX* __restrict__ gx, int H, int W, int OH,
+    int OW, int NTX, int NTY, int ntiles) {
+    __shared__ __attribute__((aligned(16))) bf16_t sg[SB_GR * SB_GC * SQ_PS];
+    __shared__ __attribute__((aligned(16))) bf16_t swb[SQ_WN + 8];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    constexpr int NWQ = (3 * 49 * 8 + 255) / 256, NGQ = (SB_GR * SB_GC * 8 + 255) / 256;
+    // tiles in the order x, y, image; workgroup i of G takes the consecutive tiles [i ntiles / G, (i + 1) ntiles / G)
+    const int t0 = (int)((long long)blockIdx.x * ntiles / gridDim.x), t1 = (int)((long long)(blockIdx.x + 1) * ntiles / gridDim.x);
+    int n, ih0, iw0;                                       // the tile being computed
+    u32x4 gv[NGQ];                                         // the g_y1 tile on its way from global memory to LDS
+    unsigned gok = 0;
+    // every global load of a tile is in flight before the first LDS store, as in the class form; here the loads of tile
+    // t + 1 are issued in front of the MFMAs of tile t and land in LDS behind them
+    auto tile_load = [&](int t, int& tn, int& tih0, int& tiw0) {
+        const int tx = t % NTX, r = t / NTX;
+        tn = r / NTY;
+        tih0 = (r - tn * NTY) * SB_TH;
+        tiw0 = tx * SB_TW;
+        const int ohb = tih0 / 2 - 1, owb = tiw0 / 2 - 1;
+        gok = 0;
+#pragma unroll
+        for (int j = 0; j < NGQ; ++j) {
+            const int q = tid + 256 * j < SB_GR * SB_GC * 8 ? tid + 256 * j : SB_GR * SB_GC * 8 - 1;
+            const int ch = q & 7, px = q >> 3;
+            const int row = px / SB_GC, col = px - row * SB_GC;
+            const int oh = ohb + row, ow = owb + col;
+            const bool ok = (oh >= 0) && (oh < OH) && (ow >= 0) && (ow < OW);
+            gok |= ok ? 1u << j : 0u;
+            gv[j] = *reinterpret_cast<const u32x4*>(gy + (((size_t)tn * OH + (ok ? oh : 0)) * OW + (ok ? ow : 0)) * 64 + ch * 8);
+        }
+    };
+    auto tile_to_lds = [&]() {
+#pragma unroll
+        for (int j = 0; j < NGQ; ++j) {
+            const int q = tid + 256 * j;
+            const int ch = q & 7, px = q >> 3;
+            u32x4 t = gv[j];
+            if (!(gok >> j & 1u)) t = u32x4{0u, 0u, 0u, 0u};
+            if (q < SB_GR * SB_GC * 8) *reinterpret_cast<u32x4*>(sg + px * SQ_PS + ch * 8) = t;
+        }
+    };
+    {
+        u32x4 wv[NWQ];
+#pragma unroll
+        for (int j = 0; j < NWQ; ++j) {
+            const int q = tid + 256 * j < 3 * 49 * 8 ? tid + 256 * j : 3 * 49 * 8 - 1;
+            wv[j] = *reinterpret_cast<const u32x4*>(wb + q * 8);
+        }
+        tile_load(t0, n, ih0, iw0);
+#pragma unroll
+        for (int j = 0; j < NWQ; ++j) {
+            const int q = tid + 256 * j;
+            const int ci = q / (49 * 8), r = q - ci * 49 * 8, tap = r >> 3, ch = r & 7, kh = tap / 7, kw = tap - kh * 7;
+            if (q < 3 * 49 * 8) *reinterpret_cast<u32x4*>(swb + ci * SQ_WCI + kh * SQ_WKH + kw * 64 + ch * 8) = wv[j];
+        }
+        if (tid == 0) *reinterpret_cast<u32x4*>(swb + SQ_WN) = u32x4{0u, 0u, 0u, 0u};
+        tile_to_lds();
+    }
+    lds_sync();
+    const int l16 = lane & 15, ks = lane >> 4;             // B: pixel column / K slice.  A: row 4 * class + ci / K slice
+    const int ci = l16 & 3, ca = l16 >> 3, cb = (l16 >> 2) & 1;
+    // A fragment of shift (dr, dc), half cg: abase - 2 dr SQ_WKH - 2 dc 64 + 32 cg, or the zero chunk
+    const int abase = (ci < 3 ? ci : 0) * SQ_WCI + (ca + 3) * SQ_WKH + (cb + 3) * 64 + 8 * ks;
+    const bool okc = ci < 3, oka = okc && ca == 1, okb = okc && cb == 1, okab = oka && cb == 1;
+    // B fragment of sub-row q: bbase + ((q + dr) SB_GC + dc) SQ_PS + 32 cg
+    const int bbase = ((2 * w + 1) * SB_GC + l16 + 1) * SQ_PS + 8 * ks;
+#pragma unroll 1
+    for (int t = t0; t < t1; ++t) {
+        int nn = 0, nih0 = 0, niw0 = 0;
+        if (t + 1 < t1) tile_load(t + 1, nn, nih0, niw0);
+        f32x4 acc[2];
+        acc[0] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        acc[1] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
+        // 32 steps s = (shift, cg), the LDS reads of step s + SQ_AHEAD issued in front of the MFMAs of step s
+        constexpr int SQ_AHEAD = 2;
+        bf16x8 fa[SQ_AHEAD + 1], fb[SQ_AHEAD + 1][2];
+#pragma unroll
+        for (int s = 0; s < 32 + SQ_AHEAD; ++s) {
+            if (s < 32) {
+                const int dr = 2 - (s >> 3), dc = 2 - ((s >> 1) & 3), cg = s & 1, f = s % (SQ_AHEAD + 1);
+                const bool ok = dr == 2 ? (dc == 2 ? okab : oka) : (dc == 2 ? okb : okc);
+                fa[f] = lds8(swb + (ok ? abase - 2 * dr * SQ_WKH - 2 * dc * 64 + 32 * cg : SQ_WN));
+#pragma unroll
+                for (int q = 0; q < 2; ++q) fb[f][q] = lds8(sg + bbase + ((q + dr) * SB_GC + dc) * SQ_PS + 32 * cg);
+            }
+            if (s >= SQ_AHEAD) {
+                const int f = (s - SQ_AHEAD) % (SQ_AHEAD + 1);
+#pragma unroll
+                for (int q = 0; q < 2; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[f], fb[f][q], acc[q], 0, 0, 0);
+            }
+        }
+        // lane group ks holds class ks = 2 A + BB: the iw pair of one output row sits in lanes l (BB = 0) and l + 16 (BB = 1)
+        const int iw = iw0 + 2 * l16;
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int ih = ih0 + 2 * (2 * w + q) + (ks >> 1);
+            float v[3], o[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                v[c] = acc[q][c] * nm.inv_std[c];
+                o[c] = __shfl_down(v[c], 16);
+            }
+            if (!(ks & 1) && ih < H && iw < W) {
+#pragma unroll
+                for (int c = 0; c < 3; ++c) st_pair<TX>(gx + (((size_t)n * 3 + c) * H + ih) * W + iw, v[c], o[c]);
+            }
+        }
+        if (t + 1 < t1) {                                  // uniform over the workgroup
+            lds_sync();                                    // every wave is done reading tile t
+            tile_to_lds();
+            n = nn; ih0 = nih0; iw0 = niw0;
+            lds_sync();
+        }
+    }
+}
+
+// adil_stem_bwd_variant: which kernels adil_stem_pool_bwd and adil_stem_conv_bwd launch (0 = the quad and shift forms,
+// 1 = the gather and class forms they replaced: the measuring baseline and the bitwise reference).  Read at launch.
+static int g_stem_bwd_variant = 0;
+
 }  // namespace
+
+extern "C" int adil_stem_bwd_variant(int variant) {
+    const int prev = g_stem_bwd_variant;
+    if (variant == 0 || variant == 1) g_stem_bwd_variant = variant;
+    return prev;
+}
 
 // ------------------------------------------------------------------------------------------------------------ //
 extern "C" int adil_stem_conv_fwd(const void* x, int x_dtype, const void* w_fwd, float mean0, float mean1, float mean2,
@@ -406,6 +638,14 @@ extern "C" int adil_stem_pool_bwd(const void* g, const uint8_t* idx, const void*
     ADIL_ENTER();
     if (!g || !idx || !p || !scale || !gy || B <= 0 || OH <= 0 || OW <= 0 || C <= 0 || (C & 7)) return ADIL_EINVAL;
     const int PH = (OH - 1) / 2 + 1, PW = (OW - 1) / 2 + 1;
+    // the quad form takes (n, a) from blockIdx.x and a chunk of (b, c8) from blockIdx.y; grids beyond it keep the gather form
+    const long long rows = (long long)B * PH, cols = ((long long)PW * (C / 8) + 255) / 256;
+    if (g_stem_bwd_variant == 0 && rows <= 0x7fffffffLL && cols <= 65535) {
+        hipLaunchKernelGGL(stem_pool_bwd_quad_kernel, dim3((unsigned)rows, (unsigned)cols), dim3(256), 0, (hipStream_t)stream,
+                           (const bf16_t*)g, idx, (const bf16_t*)p, scale, (bf16_t*)gy, OH, OW, PH, PW, C / 8);
+        ADIL_CHECK_LAUNCH();
+        return 0;
+    }
     const size_t total = (size_t)B * OH * OW * (C / 8);
     hipLaunchKernelGGL(stem_pool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
                        (const bf16_t*)g, idx, (const bf16_t*)p, scale, (bf16_t*)gy, B, OH, OW, PH, PW, C / 8);
@@ -422,6 +662,21 @@ extern "C" int adil_stem_conv_bwd(const void* gy, const void* w_bwd, float inv_s
     const int OH = H / 2, OW = W / 2;
     const dim3 grid((W + SB_TW - 1) / SB_TW, (H + SB_TH - 1) / SB_TH, B);
     hipStream_t st = (hipStream_t)stream;
+    const long long ntiles = (long long)grid.x * grid.y * B;
+    if (g_stem_bwd_variant == 0 && ntiles <= 0x7fffffffLL) {     // (a tile list beyond 32 bits keeps the class form)
+        // one resident set of workgroups (3 per CU), each walking its share of the tiles: the weights are staged once per
+        // workgroup and the g_y1 loads of a tile run under the MFMAs of the tile before it
+        const long long slots = 3LL * adil_num_cu();
+        const dim3 lin((unsigned)(ntiles < slots ? ntiles : slots));
+        if (gx_dtype == ADIL_F32)
+            hipLaunchKernelGGL(stem_conv_bwd_shift_kernel<float>, lin, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd, nm,
+                               (float*)gx, H, W, OH, OW, (int)grid.x, (int)grid.y, (int)ntiles);
+        else
+            hipLaunchKernelGGL(stem_conv_bwd_shift_kernel<bf16_t>, lin, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd,
+                               nm, (bf16_t*)gx, H, W, OH, OW, (int)grid.x, (int)grid.y, (int)ntiles);
+        ADIL_CHECK_LAUNCH();
+        return 0;
+    }
     if (gx_dtype == ADIL_F32)
         hipLaunchKernelGGL(stem_conv_bwd_kernel<float>, grid, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd, nm,
                            (float*)gx, H, W, OH, OW);

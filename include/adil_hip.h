@@ -55,7 +55,7 @@ extern "C" {
  * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those, and
  * adil_dense3x3_fwd / adil_dense3x3_bwd after those, and their row-pitch forms adil_dense1x1_fwd_ld / adil_dense1x1_bwd_ld /
  * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those, and adil_bn_pool_head_fwd / adil_bn_pool_head_bwd after those: all additive
- * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy / adil_conv3x3_loop (test and tool entry points: the
+ * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy / adil_conv3x3_loop / adil_stem_bwd_variant (test and tool entry points: the
  * product calls none of them). */
 int adil_abi_version(void);
 
@@ -321,6 +321,17 @@ int adil_stem_pool_bwd(const void* g, const uint8_t* idx, const void* p, const f
                        int C, void* stream);
 int adil_stem_conv_bwd(const void* gy, const void* w_bwd, float inv_std0, float inv_std1, float inv_std2, void* gx,
                        int gx_dtype, int B, int H, int W, void* stream);
+/* adil_stem_bwd_variant sets which kernels adil_stem_pool_bwd and adil_stem_conv_bwd launch (a host-side int read at
+ * launch; 0 = the default: the un-pooling as one thread per 2 x 2 quad of conv-output pixels with its four windows loaded
+ * up front, and the 7x7 input gradient as one MFMA per (g_y1 shift, channel half) for all four input-pixel parity classes;
+ * 1 = the kernels they replaced — one thread per pixel gathering its windows, one parity class after another — kept as the
+ * measuring baseline and the bitwise reference) and returns the previous value; any other argument changes nothing and
+ * only returns the current value.  For tests and tools: the product does not call it.
+ * Both values give the same bits for every input of adil_stem_pool_bwd, and for every FINITE gy of adil_stem_conv_bwd.
+ * Under 0 the four classes share the MFMA, so a non-finite gy value meets the zero weights of the classes that have no
+ * tap at its shift: 0 * inf = NaN then also reaches input pixels of another parity whose own taps do not read that value
+ * (under 1 those pixels stay finite). */
+int adil_stem_bwd_variant(int variant);
 
 /* Pointwise (1x1) convolution of the frozen network on channels_last storage, with the eval-BatchNorm / residual /
  * ReLU epilogue applied to the accumulators (bf16 in/out, fp32 accumulate):
