@@ -70,6 +70,10 @@ class Arith:
             acc = acc + a[:, k0:k0 + self.chunk] @ b[k0:k0 + self.chunk]
         return acc
 
+    def f32(self, v):
+        """A value the kernels hold in an fp32 register."""
+        return v.float()
+
     def rnd(self, v):
         return bf16_trunc(v) if "trunc" in self.mut else bf16_rne(v)
 
@@ -91,6 +95,27 @@ class Arith:
         if not self.ref or eps is None:
             return r, None
         return r, (bf16_rne((v + eps).float()) - bf16_rne((v - eps).float())).double().abs()
+
+
+class Unrounded(Arith):
+    """The reference with every rounding taken out: fp32 registers are fp64, `rnd` is the identity, no candidate differs.
+    Each restatement is then the plain real-valued function it rounds (tests/resnet_tape.py holds a whole network's
+    call sequence to the fp64 torch modules with it)."""
+
+    def __init__(self, mut=()):
+        super().__init__(F64, None, mut)
+
+    def f32(self, v):
+        return v.double()
+
+    def rnd(self, v):
+        return v
+
+    def affine_rnd(self, x, s, b):
+        return x.double() * s.double() + b.double(), None
+
+    def window_rnd(self, v, eps):
+        return v, (None if eps is None else torch.zeros_like(v))
 
 
 class Out(NamedTuple):
@@ -175,17 +200,17 @@ def pw_bwd(ar, g, wt, scale, y=None, g2=None, relu=1, xin=None, pscale=None, psh
     kernel's order (no contraction can change them: the only product next to a sum is by 0 or 1)."""
     dt = ar.dtype
     M, N = g.shape
-    v = g.float()
+    v = ar.f32(g)
     S = g.to(dt).abs()
     if g2 is not None:
-        v = v + g2.float()
+        v = v + ar.f32(g2)
         S = S + g2.to(dt).abs()
     if g3 is not None:
         u = up2(g3, M, sub_w, sub_hw, "g3_odd" in ar.mut)
-        v = v + u.float()
+        v = v + ar.f32(u)
         S = S + u.to(dt).abs()
     mask = ar.pos(y.to(dt)) if relu else None
-    gz = ar.rnd(v * scale.float()).to(dt)
+    gz = ar.rnd(v * ar.f32(scale)).to(dt)
     if mask is not None:
         gz = torch.where(mask, gz, torch.zeros_like(gz))
     acc = ar.mm(gz, wt.to(dt).t())
@@ -199,7 +224,7 @@ def pw_bwd(ar, g, wt, scale, y=None, g2=None, relu=1, xin=None, pscale=None, psh
     ps, pb = pscale.to(dt), pshift.to(dt)
     eps = acc_eps(Sx, N) if ar.ref else None
     gx1, d1 = ar.window_rnd(acc, eps)
-    cond = xin.float() * pscale.float() + pshift.float() > 0           # separate fp32 roundings
+    cond = ar.f32(xin) * ar.f32(pscale) + ar.f32(pshift) > 0           # separate fp32 roundings
     alt = None
     if ar.ref:
         alt = (xin.double() * ps + pb).float() > 0                     # contracted to an FMA
@@ -244,7 +269,7 @@ def join_bwd(ar, g_h1, h1, scale1, wt1, g_out, out, scale3, wt3, h2raw, pscale2,
     wt1 [C][W], wt3 [W][C]."""
     dt = ar.dtype
     m1, m3 = ar.pos(h1.to(dt)), ar.pos(out.to(dt))
-    x0 = ar.rnd(g_h1.float() * scale1.float()).to(dt)
+    x0 = ar.rnd(ar.f32(g_h1) * ar.f32(scale1)).to(dt)
     x0 = torch.where(m1, x0, torch.zeros_like(x0))
     T1, T3 = wt1.to(dt), wt3.to(dt)
     acc_t = ar.mm(x0, T1.t())
@@ -268,7 +293,7 @@ def join_bwd(ar, g_h1, h1, scale1, wt1, g_out, out, scale3, wt3, h2raw, pscale2,
         if bool(dz.any()):
             eps = eps + torch.where(m3, dz, torch.zeros_like(dz)) @ T3.abs().t()
     gx1, d1 = ar.window_rnd(acc, eps)
-    cond = h2raw.float() * pscale2.float() + pshift2.float() > 0
+    cond = ar.f32(h2raw) * ar.f32(pscale2) + ar.f32(pshift2) > 0
     alt = None
     if ar.ref:
         alt = (h2raw.double() * ps + pb).float() > 0
