@@ -78,7 +78,7 @@ class FCOut(NamedTuple):
 def finish(ar, o):
     """The output tensor (values, in the arithmetic's dtype) of an FCOut; a clamped non-positive value and a zero are +0."""
     v = o.pre.clamp(0.0, 6.0) + 0.0 if o.act else o.pre + 0.0
-    v = ar.rnd(v) if o.dtype == BF16 else v.float().to(v.dtype)
+    v = ar.rnd(v) if o.dtype == BF16 else ar.f32(v).to(v.dtype)
     if "neg_zero" in ar.mut:                                           # mutant: -0.0 is emitted
         v = torch.where(v == 0, torch.full_like(v, -0.0), v)
     return v
@@ -89,14 +89,15 @@ def expected(o):
     return o.pre.clamp(0.0, 6.0) if o.act else o.pre
 
 
-def _table(v, like):
-    return torch.tensor(v, dtype=F32, device=like.device).view(1, 3, 1, 1)
+def _table(ar, v, like):
+    """Three floats as the kernel receives them: fp32 arguments (`ar.f32`: the doubles themselves over `Unrounded`)."""
+    return ar.f32(torch.tensor(v, dtype=F64, device=like.device)).view(1, 3, 1, 1)
 
 
 def normalise(ar, x, mean, inv_std):
     """x' as the kernel forms it: two fp32 operations no contraction can merge, one rounding to bf16.  Unpadded."""
-    m, s = _table(mean, x), _table(inv_std, x)
-    d = x.float() + m if "mean_sign" in ar.mut else x.float() - m
+    m, s = _table(ar, mean, x), _table(ar, inv_std, x)
+    d = ar.f32(x) + m if "mean_sign" in ar.mut else ar.f32(x) - m
     v = d * s
     return v if "no_round_x" in ar.mut else ar.rnd(v)
 
@@ -132,7 +133,7 @@ def first_fwd(ar, x, w, mean, inv_std, scale, shift, relu6=1):
 
 def round_gz(ar, g, scale):
     """bf16(g * scale) as the kernel forms it: one fp32 product, one rounding."""
-    v = g.float() if "no_scale_bwd" in ar.mut else g.float() * scale.float()
+    v = ar.f32(g) if "no_scale_bwd" in ar.mut else ar.f32(g) * ar.f32(scale)
     return ar.rnd(v)
 
 
@@ -163,7 +164,7 @@ def first_bwd(ar, g, y, scale, w, inv_std, H, W, relu6=1, out_dtype=BF16):
                 S[:, kh:kh + 2 * OH - 1:2, kw:kw + 2 * OW - 1:2] += (gs.abs() @ wt.abs()).reshape(B, OH, OW, 3)
     o = 0 if "parity" in ar.mut else 1                                 # mutant: (h - kh) / 2 instead of (h + 1 - kh) / 2
     crop = lambda a: a[:, o:H + o, o:W + o].permute(0, 3, 1, 2).contiguous()
-    istd = _table(inv_std, g).to(dt)
+    istd = _table(ar, inv_std, g).to(dt)
     if "no_inv_std" in ar.mut:
         istd = torch.ones_like(istd)
     return FCOut(crop(acc) * istd + 0.0, None if S is None else crop(S) * istd.abs(), 128, False, out_dtype)

@@ -46,7 +46,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
-from classifier_reference import BF16, CANARY, F32, Arith, bf16_rne, rng  # noqa: F401  (CANARY: re-exported to the tests)
+from classifier_reference import BF16, CANARY, F32, Arith, Unrounded, bf16_rne, rng  # noqa: F401  (CANARY: re-exported to the tests)
 
 F64 = torch.float64
 POOL_ROWS = 8                    # pixel rows of a pooling workgroup (hw = r, r + 8, ...)
@@ -130,13 +130,15 @@ def pool_sum(ar, x):
     return s, None
 
 
-def scale_f32(v, HW):
-    """f32(f32(v) * inv_hw): the ONE fp32 multiply of both passes, bit exact."""
+def scale_f32(v, HW, ar=None):
+    """f32(f32(v) * inv_hw): the ONE fp32 multiply of both passes, bit exact.  Over `Unrounded` alone: the real v / HW."""
+    if isinstance(ar, Unrounded):
+        return v.double() / HW
     return v.float() * inv_hw(HW).to(v.device)
 
 
 def pooled_of(ar, S, HW):
-    p = scale_f32(S, HW)
+    p = scale_f32(S, HW, ar)
     if "pooled_bf16" in ar.mut:                                         # mutant: the pooled features are rounded to bf16
         p = bf16_rne(p)
     return p
@@ -162,7 +164,8 @@ def gpooled_of(ar, g, w):
 
 def gx_of(ar, gpooled, HW):
     """[B][HW][C] bf16 values from the STORED fp32 gpooled: one fp32 multiply, one rounding (`ar.rnd`: the `trunc` mutant)."""
-    v = ar.rnd(scale_f32(gpooled, HW)).bfloat16()
+    v = ar.rnd(scale_f32(gpooled, HW, ar))
+    v = v if isinstance(ar, Unrounded) else v.bfloat16()
     return v[:, None, :].expand(v.shape[0], HW, v.shape[1]).contiguous()
 
 

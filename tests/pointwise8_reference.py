@@ -143,7 +143,7 @@ def pw8_fwd(ar, x, w, scale, shift, res=None, act=0):
 
 def round_gz(ar, g, scale):
     """bf16(g * scale) as the kernel forms it: one fp32 product, one rounding."""
-    v = g.float() if "no_scale_bwd" in ar.mut else g.float() * scale.float()
+    v = ar.f32(g) if "no_scale_bwd" in ar.mut else ar.f32(g) * ar.f32(scale)
     return ar.rnd(v)
 
 
