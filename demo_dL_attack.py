@@ -109,6 +109,11 @@ def build_parser():
                         '(engine.precise_head), always = in every classifier call; 0 (default) = the library pooling and '
                         'bf16 linear layer.  Independent of the other three; with all four no library call is left in the '
                         'classifier.  Ignored otherwise')
+    p.add_argument('--own-attention', type=int, default=0, choices=[0, 1],
+                   help='-m vit --dtype bf16: 1 = the self-attention between the in-projection and the out-projection of the '
+                        '12 encoder blocks runs in the whole-head attention kernels (no score matrix, softmax or permuted '
+                        'copy is written); 0 (default) = plain library matmuls and softmax.  The projections, the MLP, '
+                        'LayerNorm and GELU stay on the library.  Ignored otherwise')
     return p
 
 
@@ -184,10 +189,12 @@ def main(args):
                       and zoo.canonical_name(model_name) == 'densenet121')
     own_dense_head = ({'0': False, 'inference': 'inference', 'always': True}[args.own_dense_head]
                       if dtype == torch.bfloat16 and zoo.canonical_name(model_name) == 'densenet121' else False)
+    own_attention = (bool(args.own_attention) and dtype == torch.bfloat16
+                     and zoo.canonical_name(model_name) == 'vit_b_16')
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
                                  channels_last=(fast or own_dw or own_pw or own_fc or bool(own_head) or own_dense
                                                 or own_dense_conv or own_dense_stem or bool(own_dense_head)),
-                                 own_dense_head=own_dense_head,
+                                 own_dense_head=own_dense_head, own_attention=own_attention,
                                  own_dense_transition=own_dense_transition, own_dense_stem=own_dense_stem,
                                  own_depthwise=own_dw, own_pointwise=own_pw, own_dense_pointwise=own_dense,
                                  own_dense_conv=own_dense_conv, own_dense_block=own_dense_block,

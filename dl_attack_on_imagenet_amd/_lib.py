@@ -110,6 +110,9 @@ SIGNATURES = {
                                           c_void_p]),
     "adil_dense_transition_bwd": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                           c_int, c_int, c_int, c_void_p]),
+    "adil_attn_max_tokens": (c_int, []),
+    "adil_attn_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "adil_attn_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
 }
 
 ABI_VERSION = 8

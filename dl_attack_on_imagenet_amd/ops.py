@@ -1732,6 +1732,67 @@ def bn_pool_head(x: Tensor, pscale: Tensor, pshift: Tensor, w: Tensor, wt: Tenso
 
 
 # --------------------------------------------------------------------------- #
+ATTN_HEAD_DIM = 64                           # head dimension of adil_attn_fwd / _bwd (include/adil_hip.h)
+_attn_max_tokens = None
+
+
+def attention_max_tokens() -> int:
+    """adil_attn_max_tokens(): the longest sequence one workgroup's LDS holds."""
+    global _attn_max_tokens
+    if _attn_max_tokens is None:
+        _attn_max_tokens = int(_lib.load().adil_attn_max_tokens())
+    return _attn_max_tokens
+
+
+def attention_covers(qkv: Tensor, heads: int) -> bool:
+    """What adil_attn_fwd / _bwd accept: a CUDA, bf16, contiguous [B, T, 3 * heads * 64] in-projection output with
+    1 <= T <= adil_attn_max_tokens() (anything else is ADIL_EINVAL and the caller keeps the torch statements)."""
+    return (qkv.dim() == 3 and qkv.is_cuda and qkv.dtype == torch.bfloat16 and heads >= 1
+            and qkv.shape[2] == 3 * heads * ATTN_HEAD_DIM and qkv.shape[0] >= 1 and qkv.shape[0] * heads <= 2 ** 31 - 1
+            and qkv.is_contiguous() and 1 <= qkv.shape[1] <= attention_max_tokens())
+
+
+class AttentionFunction(torch.autograd.Function):
+    """softmax(q k^T / 8) v for every (image, head) of an in-projection output, one launch each way (adil_attn_fwd /
+    adil_attn_bwd): qkv is read where the in-projection wrote it and o is written where the out-projection reads it.  The
+    forward saves qkv, o and the fp32 log-sum-exp [B][H][T]; the backward recomputes the probabilities from them.  o, lse
+    and gqkv come from the torch allocator (the call is capturable)."""
+
+    @staticmethod
+    def forward(ctx, qkv, heads):
+        lib = _lib.load()
+        b, t, _ = qkv.shape
+        o = torch.empty((b, t, heads * ATTN_HEAD_DIM), dtype=torch.bfloat16, device=qkv.device)
+        lse = torch.empty((b, heads, t), dtype=torch.float32, device=qkv.device)
+        _lib.check(lib.adil_attn_fwd(_ptr(qkv), _ptr(o), _ptr(lse), b, t, heads, _stream()), "adil_attn_fwd")
+        ctx.save_for_backward(qkv, o, lse)
+        ctx.heads = heads
+        return o
+
+    @staticmethod
+    def backward(ctx, go):
+        lib = _lib.load()
+        qkv, o, lse = ctx.saved_tensors
+        b, t, _ = qkv.shape
+        if go.dtype != torch.bfloat16 or go.shape != o.shape:
+            raise ValueError(f"the output gradient must be a bfloat16 {tuple(o.shape)} tensor, got {go.dtype} {tuple(go.shape)}")
+        go2 = go if go.is_contiguous() else go.contiguous()
+        gqkv = torch.empty_like(qkv)
+        _lib.check(lib.adil_attn_bwd(_ptr(qkv), _ptr(o), _ptr(lse), _ptr(go2), _ptr(gqkv), b, t, ctx.heads, _stream()),
+                   "adil_attn_bwd")
+        return gqkv, None
+
+
+def attention(qkv: Tensor, heads: int) -> Tensor:
+    """qkv (B, T, 3 * heads * 64) bf16, the in-projection output as it lies in memory -> o (B, T, heads * 64) bf16, the
+    out-projection's input; no copy of either."""
+    if not attention_covers(qkv, heads):
+        raise ValueError(f"adil_attn does not cover a {tuple(qkv.shape)} {qkv.dtype} tensor on {qkv.device} with {heads} heads "
+                         f"(bf16, contiguous, head dimension {ATTN_HEAD_DIM}, at most {attention_max_tokens()} tokens)")
+    return AttentionFunction.apply(qkv, heads)
+
+
+# --------------------------------------------------------------------------- #
 class DictSynthFunction(torch.autograd.Function):
     """x + D v[index] as a differentiable op (the tensordot of adil.py:25 and its autograd backward).
     grad wrt v is dense (N,K) with zero rows outside `index`, exactly what autograd produces."""

@@ -192,6 +192,7 @@ class _EncoderBlock(nn.Module):
     def __init__(self, heads, dim, mlp_dim):
         super().__init__()
         self.heads = heads
+        self.own_attention = False                       # use_own_attention_: the whole-head attention kernels
         self.ln_1 = nn.LayerNorm(dim, eps=1e-6)
         self.self_attention = nn.MultiheadAttention(dim, heads, batch_first=True)   # parameter container (torchvision names)
         self.ln_2 = nn.LayerNorm(dim, eps=1e-6)
@@ -199,11 +200,17 @@ class _EncoderBlock(nn.Module):
 
     def _attention(self, y):
         """Plain-matmul self attention with the MultiheadAttention parameters.  The fused SDPA / native-MHA kernels of
-        this PyTorch-ROCm build raised a GPU memory access fault on ViT-B/16 (197 tokens, bf16), so they are not used."""
+        this PyTorch-ROCm build raised a GPU memory access fault on ViT-B/16 (197 tokens, bf16), so they are not used.
+        With `own_attention` on, and where `ops.attention_covers` holds (CUDA, bf16, head dimension 64, a sequence one
+        workgroup's LDS holds), the segment between the two projections is `ops.attention`: it reads the in-projection's
+        output and writes the out-projection's input in place, so no score matrix, softmax or permuted copy is written."""
         att = self.self_attention
         b, t, dim = y.shape
         hd = dim // self.heads
-        qkv = F.linear(y, att.in_proj_weight, att.in_proj_bias).reshape(b, t, 3, self.heads, hd).permute(2, 0, 3, 1, 4)
+        qkv = F.linear(y, att.in_proj_weight, att.in_proj_bias)
+        if self.own_attention and hd == ops.ATTN_HEAD_DIM and ops.attention_covers(qkv, self.heads):
+            return F.linear(ops.attention(qkv, self.heads), att.out_proj.weight, att.out_proj.bias)
+        qkv = qkv.reshape(b, t, 3, self.heads, hd).permute(2, 0, 3, 1, 4)
         q, k, v = qkv[0], qkv[1], qkv[2]                                   # (b, heads, t, hd)
         w = torch.softmax((q @ k.transpose(-1, -2)) * (hd ** -0.5), dim=-1)
         out = (w @ v).permute(0, 2, 1, 3).reshape(b, t, dim)
@@ -1426,6 +1433,21 @@ def use_own_dense_head_(net: nn.Module, mode=True) -> int:
     return 1
 
 
+def use_own_attention_(net: nn.Module) -> int:
+    """Route the self-attention of every `_EncoderBlock` of `net` through the whole-head attention kernels
+    (`ops.attention`) wherever they cover the input; a block keeps the plain-matmul statements for every other input (CPU,
+    fp32, a head dimension other than 64, too many tokens).  No parameter or buffer changes: state-dict keys stay as they
+    are.  Returns how many blocks were switched (12 for ViT-B/16)."""
+    n = 0
+    for m in net.modules():
+        if isinstance(m, _EncoderBlock):
+            m.own_attention = True
+            n += 1
+    if n == 0:
+        raise ValueError("own attention is a switch of the VisionTransformer's encoder blocks; this network has none")
+    return n
+
+
 class FusedResNet(nn.Module):
     """A frozen ResNet whose BatchNorm(eval) / residual add / ReLU run as ONE elementwise kernel per convolution
     (`ops.affine_act`, forward and input-gradient backward) instead of 2-3 separate PyTorch kernels.  Convolution
@@ -1545,7 +1567,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      own_first_conv: bool = False, own_dense_pointwise: bool = False,
                      own_dense_conv: bool = False, own_dense_block: bool = False,
                      own_dense_transition: bool = False, own_dense_stem: bool = False,
-                     own_dense_head=False) -> nn.Module:
+                     own_dense_head=False, own_attention: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
     fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
     default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
@@ -1579,7 +1601,11 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     `ops.bn_pool_head`): True = in every call, "inference" = only inside engine.precise_head (the DDrague inference
     solver; the learner keeps the library head and bf16 logits), as head_fp32 does for MobileNetV2; head_fp32 itself
     stays a switch of the other networks; off by default.  With all six switches no library call is left in
-    DenseNet-121."""
+    DenseNet-121;
+    own_attention (ViT-B/16, bf16; channels_last is not needed: the tokens are rows) runs the segment between the
+    in-projection and the out-projection of the 12 encoder blocks in the whole-head attention kernels
+    (`use_own_attention_`, `ops.attention`; the projections, the MLP, LayerNorm and GELU stay on the library; off by
+    default)."""
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
@@ -1642,6 +1668,10 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         raise ValueError("own_dense_head needs a bfloat16 network (the head kernels work on bf16 activations)")
     if own_dense_head and not channels_last:
         raise ValueError("own_dense_head needs channels_last=True (the head kernels work on channels_last storage)")
+    if own_attention and key != 'vit_b_16':
+        raise ValueError("own_attention is a switch of ViT-B/16 (no other network has attention layers)")
+    if own_attention and dtype != torch.bfloat16:
+        raise ValueError("own_attention needs a bfloat16 network (the attention kernels work on bf16 activations)")
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1673,6 +1703,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
         use_own_head_(net, head_fp32)
     if own_dense_head:                   # after the weights are loaded: fp32 copies of the Linear and of norm5's affine map
         use_own_dense_head_(net, own_dense_head)
+    if own_attention:
+        use_own_attention_(net)
     if fuse_bn_act and isinstance(net, ResNet):
         stem_fused = bool(fuse_stem)
         if stem_fused and dtype != torch.bfloat16:

@@ -54,7 +54,8 @@ extern "C" {
  * same way, and adil_pw8_fwd / adil_pw8_bwd after them, and adil_first3x3_fwd / adil_first3x3_bwd after those, and
  * adil_pool_head_fwd / adil_pool_head_bwd after those, and adil_dense1x1_fwd / adil_dense1x1_bwd after those, and
  * adil_dense3x3_fwd / adil_dense3x3_bwd after those, and their row-pitch forms adil_dense1x1_fwd_ld / adil_dense1x1_bwd_ld /
- * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those, and adil_bn_pool_head_fwd / adil_bn_pool_head_bwd after those: all additive
+ * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those, and adil_bn_pool_head_fwd / adil_bn_pool_head_bwd after those, and
+ * adil_attn_max_tokens / adil_attn_fwd / adil_attn_bwd after those: all additive
  * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy / adil_conv3x3_loop / adil_stem_bwd_variant (test and tool entry points: the
  * product calls none of them). */
 int adil_abi_version(void);
@@ -653,6 +654,38 @@ int adil_dense_transition_fwd(const void* x, const float* pscale, const float* p
                               int B, int H, int W, int K, int N, void* stream);
 int adil_dense_transition_bwd(const void* g, int ldg, const void* wt, const void* xin, const float* pscale,
                               const float* pshift, void* gx, int B, int H, int W, int K, int N, void* stream);
+
+/* Whole-head self-attention of the frozen ViT-B/16 (head dimension 64), forward and input gradient, on the operands of the
+ * two linear layers around it as they lie in memory, so no permute or reshape copy remains and no score matrix is written:
+ *     qkv, gqkv [B][T][3][H][64] bf16 : the in-projection output [B][T][3 H 64]; q of head h at column h*64 + d, k at
+ *                                       H*64 + h*64 + d, v at 2*H*64 + h*64 + d
+ *     o, go     [B][T][H][64] bf16    : [B][T][H*64], what the out-projection reads
+ *     lse       [B][H][T] fp32
+ * For image b, head h, query i and key j < T:
+ *     t_ij  = 0.125 * sum_d q_id k_jd          bf16 products, fp32 accumulation on the matrix pipe in any order; the
+ *                                              factor 1/sqrt(64) is applied to the fp32 sum (exact)
+ *     m_i   = max_j t_ij;  e_ij = exp(t_ij - m_i) in fp32 (hardware exp2 behind a multiplication with log2(e))
+ *     l_i   = sum_j e_ij from the unrounded fp32 e;  lse_i = m_i + ln(l_i) in fp32 (natural logarithm)
+ *     o_id  = bf16_rne((sum_j bf16_rne(e_ij) v_jd) / l_i)    the normalisation is ONE IEEE fp32 DIVISION on the accumulator
+ *   adil_attn_bwd recomputes p_ij = exp(t_ij - lse_i), dp_ij = sum_d go_id v_jd, delta_i = sum_d f32(go_id) f32(o_id) from
+ *   the stored bf16 o (fp32 fmas, d ascending in groups of 8, the 8 groups in a fixed tree), ds_ij = p_ij (dp_ij - delta_i)
+ *   in fp32, and writes
+ *     gv_jd = bf16_rne(sum_i bf16_rne(p_ij) go_id)
+ *     gq_id = bf16_rne(0.125 * sum_j bf16_rne(ds_ij) k_jd)      gk_jd = bf16_rne(0.125 * sum_i bf16_rne(ds_ij) q_id)
+ * Tiles are padded to 32 tokens inside the kernels: keys j >= T take no part in m, l, o, gq, gk or gv and query rows
+ * i >= T add nothing to gk or gv, by SELECTION (p is set to zero there, never multiplied with a padded value).
+ * One workgroup per (b, h) holds the head in LDS: 2 images of [T rounded up to 32][72] bf16 forward (36 KiB at T = 256),
+ * 4 images and two fp32 vectors backward (146 KiB at T = 256 of the CU's 160 KiB), which sets adil_attn_max_tokens() = 256.
+ * Limits: 1 <= T <= adil_attn_max_tokens(), H >= 1, B >= 1, B * H <= 2^31 - 1 (the (image, head) pair is the grid's x
+ * index), 16-byte aligned pointers.  Anything else, or a NULL pointer: ADIL_EINVAL before any launch, outputs untouched.
+ * Every element of o, lse and gqkv is written and nothing behind them; no load or store leaves an operand's extent.
+ * Element offsets are 64-bit.  One launch per call on `stream`, no allocation, no synchronisation.  No atomics: bitwise
+ * reproducible across calls and processes; capturable.  Behaviour for non-finite inputs is not promised beyond the rule
+ * that no access leaves the extents. */
+int adil_attn_max_tokens(void);
+int adil_attn_fwd(const void* qkv, void* o, float* lse, int B, int T, int H, void* stream);
+int adil_attn_bwd(const void* qkv, const void* o, const float* lse, const void* go, void* gqkv, int B, int T, int H,
+                  void* stream);
 
 #ifdef __cplusplus
 }
