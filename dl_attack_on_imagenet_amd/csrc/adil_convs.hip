@@ -875,14 +875,12 @@ namespace {
 
 #define C3_LS 72
 
-// LOOP picks the main loop; both give the same bits (the same MFMA sequence per accumulator: chunk -> tap -> ks):
-//   1  a run-time loop over (chunk, tap) steps: the barrier closes a tap, and the tap behind it reads its first
-//      fragments right in front of its first MFMAs
-//   0  a run-time loop over chunks with the 9 taps unrolled (constant kh, kw, mask bit; one 32-bit weight offset per
-//      thread plus a scalar), two fragment register sets so that the LDS reads of ks + 1 fly under the MFMAs of ks, and
-//      the barrier between the MFMAs of ks = 2 and ks = 3: the first fragments of the next tap are read under ks = 3.
-//      A masked tap reads a row of zeros instead of selecting on the fragments (the centre tap needs neither).
-template <int BN, int WPX, int LOOP>                    // WPX waves along pixels (64 each) x 4/WPX along channels
+// The main loop: a run-time loop over 64-channel chunks with the 9 taps unrolled (constant kh, kw, mask bit; one 32-bit
+// weight offset per thread plus a scalar), two fragment register sets so that the LDS reads of ks + 1 fly under the MFMAs
+// of ks, and the barrier between the MFMAs of ks = 2 and ks = 3: the first fragments of the next tap are read under
+// ks = 3.  A masked tap reads a row of zeros instead of selecting on the fragments (the centre tap needs neither).  Per
+// accumulator the MFMAs run chunk -> tap -> ks (tests/golden/retired_variant_bits.json holds the bits of that order).
+template <int BN, int WPX>                              // WPX waves along pixels (64 each) x 4/WPX along channels
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv3x3_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, bf16_t* __restrict__ y, int M, int H, int W, int C, int N,
     int MT, int NT) {
@@ -929,30 +927,12 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     }
 
     u32x4 xr[XCHK], wr[3][WCH];                           // weight tiles are requested THREE taps ahead (an L2 round trip
-    [[maybe_unused]] auto load_x = [&](int cc) {         // is ~5x the 16 MFMAs of one tap)
-#pragma unroll
-        for (int i = 0; i < XCHK; ++i) {
-            const int q = tid + 256 * i, px = q >> 3, ch = q & 7;
-            int gm = m0 - W - 1 + (px < NP ? px : NP - 1);
-            gm = gm < 0 ? 0 : (gm >= M ? M - 1 : gm);
-            xr[i] = *reinterpret_cast<const u32x4*>(x + (size_t)gm * C + cc * 64 + ch * 8);
-        }
-    };
+                                                          // is ~5x the 16 MFMAs of one tap)
     auto store_x = [&]() {
 #pragma unroll
         for (int i = 0; i < XCHK; ++i) {
             const int q = tid + 256 * i, px = q >> 3, ch = q & 7;
             if (px < NP) *reinterpret_cast<u32x4*>(sx + px * C3_LS + ch * 8) = xr[i];
-        }
-    };
-    const int nit = nci * 9;
-    [[maybe_unused]] auto load_w = [&](int it, u32x4 (&r)[WCH]) {   // it = cc * 9 + tap (clamped: the surplus loads are never stored)
-        const int itc = it < nit ? it : nit - 1;
-        const int cc = itc / 9, tap = itc - 9 * cc;
-#pragma unroll
-        for (int i = 0; i < WCH; ++i) {
-            const int q = tid + 256 * i, row = q >> 3, ch = q & 7;
-            r[i] = *reinterpret_cast<const u32x4*>(wp + ((size_t)(n0 + row) * 9 + tap) * C + cc * 64 + ch * 8);
         }
     };
     auto store_w = [&](int buf, const u32x4 (&r)[WCH]) {
@@ -971,163 +951,113 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[p][ct][r] = 0.0f;
 
-    if constexpr (LOOP == 1) {
-        auto tap_body = [&](int it, u32x4 (&rfree)[WCH], const u32x4 (&rnext)[WCH]) {
-            // on entry: sw[it & 1] holds tile `it`, rnext holds tile it+1, the third register set holds tile it+2 (in
-            // flight), rfree's tile is already in LDS
-            const int buf = it & 1;
-            const int cc = it / 9, tap = it - 9 * cc;
-            const int kh = tap / 3, kw = tap - 3 * kh;
-            load_w(it + 3, rfree);
-            if (tap == 4 && cc + 1 < nci) load_x(cc + 1);             // next channel chunk's halo flies under taps 4..8
-            const bf16_t* bw = sw + (buf * BN + (wch * CTW) * 32 + c) * C3_LS + 8 * h;
-            const int shift = kh * W + kw;
-            const bool ok0 = (vmask[0] >> tap) & 1u, ok1 = (vmask[1] >> tap) & 1u;
+    // ---- addresses, once.  Weights: one 32-bit byte offset per thread (the launcher refuses packs of 2^31 elements
+    // or more) on a uniform base that advances by C per tap and 64 per chunk.  Halo: 32-bit byte offsets from the
+    // tile's first halo row (at most C3_BM + 128 rows of C elements: far below 2^32 bytes wherever the pack fits).
+    const unsigned wq = (((unsigned)(n0 + (tid >> 3)) * 9u) * (unsigned)C + (unsigned)(tid & 7) * 8u) * 2u;
+    const size_t wrow = (size_t)32 * 9 * C;                       // elements between a thread's weight rows (uniform)
+    auto load_w = [&](unsigned ws, u32x4 (&r)[WCH]) {            // ws = tap * C + cc * 64
 #pragma unroll
-            for (int ks = 0; ks < 4; ++ks) {
-                bf16x8 b0 = lds8(sx + (pl[0] + shift) * C3_LS + 16 * ks + 8 * h);
-                bf16x8 b1 = lds8(sx + (pl[1] + shift) * C3_LS + 16 * ks + 8 * h);
-                u32x4 z0 = __builtin_bit_cast(u32x4, b0), z1 = __builtin_bit_cast(u32x4, b1);
+        for (int i = 0; i < WCH; ++i)
+            r[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(wp + ws + i * wrow) + wq);
+    };
+    const int gmb = m0 - W - 1 > 0 ? m0 - W - 1 : 0;
+    const bf16_t* xb = x + (size_t)gmb * C;
+    unsigned xq[XCHK];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) { z0[j] = ok0 ? z0[j] : 0u; z1[j] = ok1 ? z1[j] : 0u; }
-                b0 = __builtin_bit_cast(bf16x8, z0);
-                b1 = __builtin_bit_cast(bf16x8, z1);
+    for (int i = 0; i < XCHK; ++i) {
+        const int px = (tid >> 3) + 32 * i;
+        int gm = m0 - W - 1 + (px < NP ? px : NP - 1);
+        gm = gm < 0 ? 0 : (gm >= M ? M - 1 : gm);
+        xq[i] = ((unsigned)(gm - gmb) * (unsigned)C + (unsigned)(tid & 7) * 8u) * 2u;
+    }
+    auto load_x = [&](int cc) {
 #pragma unroll
-                for (int ct = 0; ct < CTW; ++ct) {
-                    const bf16x8 a = lds8(bw + ct * 32 * C3_LS + 16 * ks);
-                    mma16(acc[0][ct], a, b0);
-                    mma16(acc[1][ct], a, b1);
-                }
-            }
-            if (it + 1 < nit) store_w(buf ^ 1, rnext);
-            if (tap == 8 && cc + 1 < nci) {                           // all waves are done with this halo after the barrier
-                lds_barrier();
-                store_x();
-            }
+        for (int i = 0; i < XCHK; ++i)
+            xr[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(xb + cc * 64) + xq[i]);
+    };
+    bf16_t* sz = sw + 2 * BN * C3_LS;                             // [C3_LS] zeros: what a tap outside the image reads
+    const bf16_t* xl0 = sx + pl[0] * C3_LS + 8 * h;
+    const bf16_t* xl1 = sx + pl[1] * C3_LS + 8 * h;
+    const bf16_t* zl = sz + 8 * h;
+    const bf16_t* bwl = sw + ((wch * CTW) * 32 + c) * C3_LS + 8 * h;
+    // the LDS row of pixel p's fragment at a tap (a constant after unrolling); a lane past M computes a row that
+    // is never written, so the centre tap, which never leaves the image, takes no select
+    auto xrow = [&](const bf16_t* xl, unsigned vm, int tap) -> const bf16_t* {
+        const int kh = tap / 3, kw = tap - 3 * kh;
+        const bf16_t* a = xl + (kh * W + kw) * C3_LS;
+        if (tap == 4) return a;
+        return (vm & (1u << tap)) ? a : zl;
+    };
+    struct Frag {
+        bf16x8 b0, b1, a[CTW];
+    };
+    auto read_frag = [&](Frag& f, const bf16_t* p0, const bf16_t* p1, const bf16_t* bw, int ks) {
+        f.b0 = lds8(p0 + 16 * ks);
+        f.b1 = lds8(p1 + 16 * ks);
+#pragma unroll
+        for (int ct = 0; ct < CTW; ++ct) f.a[ct] = lds8(bw + ct * 32 * C3_LS + 16 * ks);
+    };
+    auto mma_frag = [&](const Frag& f) {
+#pragma unroll
+        for (int ct = 0; ct < CTW; ++ct) {
+            mma16(acc[0][ct], f.a[ct], f.b0);
+            mma16(acc[1][ct], f.a[ct], f.b1);
+        }
+    };
+
+    load_x(0);
+    load_w(0u, wr[0]);
+    load_w((unsigned)C, wr[1]);
+    load_w(2u * (unsigned)C, wr[2]);
+    store_x();
+    store_w(0, wr[0]);
+    if (tid < C3_LS / 8) reinterpret_cast<u32x4*>(sz)[tid] = u32x4{0u, 0u, 0u, 0u};
+    __syncthreads();
+    Frag fa, fb;                                                  // fa: ks 0 and 2, fb: ks 1 and 3
+    const bf16_t* p0 = xrow(xl0, vmask[0], 0);
+    const bf16_t* p1 = xrow(xl1, vmask[1], 0);
+    read_frag(fa, p0, p1, bwl, 0);
+    for (int cc = 0; cc < nci; ++cc) {
+        const bool more = cc + 1 < nci;
+        const unsigned wsc = (unsigned)cc * 64u, wsn = (unsigned)(more ? cc + 1 : cc) * 64u;   // surplus loads: clamped, never stored
+#pragma unroll
+        for (int tap = 0; tap < 9; ++tap) {                       // 9 = 3 x 3: the register-set rotation closes per chunk
+            // on entry: sw[buf] holds this tap's tile and fa its ks = 0 fragments (in flight); wr[(tap+1) % 3] holds
+            // the next tile, wr[(tap+2) % 3] the one after it (in flight), wr[tap % 3]'s tile is already in LDS
+            const int buf = (cc + tap) & 1;                       // tile cc * 9 + tap
+            const bf16_t* bw = bwl + buf * BN * C3_LS;
+            const bool last = !more && tap == 8;
+            read_frag(fb, p0, p1, bw, 1);
+            if (!last) store_w(buf ^ 1, wr[(tap + 1) % 3]);       // read last before the previous barrier
+            load_w(tap + 3 < 9 ? wsc + (unsigned)((tap + 3) * C) : wsn + (unsigned)((tap - 6) * C), wr[tap % 3]);
+            if (tap == 4 && more) load_x(cc + 1);                // next channel chunk's halo flies under taps 4..8
+            __builtin_amdgcn_sched_barrier(0);
+            mma_frag(fa);
+            __builtin_amdgcn_sched_barrier(0);
+            read_frag(fa, p0, p1, bw, 2);
+            __builtin_amdgcn_sched_barrier(0);
+            mma_frag(fb);
+            __builtin_amdgcn_sched_barrier(0);
+            read_frag(fb, p0, p1, bw, 3);
+            __builtin_amdgcn_sched_barrier(0);
+            mma_frag(fa);
+            __builtin_amdgcn_sched_barrier(0);
+            // every wave has read all of this tap's fragments and written the next tile: the barrier sits under
+            // the MFMAs of ks = 3, and so do the first reads of the next tap
             lds_barrier();
-        };
-
-        load_x(0);
-        load_w(0, wr[0]);
-        load_w(1, wr[1]);
-        load_w(2, wr[2]);
-        store_x();
-        store_w(0, wr[0]);
-        __syncthreads();
-        for (int it = 0; it < nit; it += 3) {                         // nit = 9 * nci: a multiple of 3
-            tap_body(it, wr[0], wr[1]);
-            tap_body(it + 1, wr[1], wr[2]);
-            tap_body(it + 2, wr[2], wr[0]);
-        }
-    } else {
-        // ---- addresses, once.  Weights: one 32-bit byte offset per thread (the launcher refuses packs of 2^31 elements
-        // or more) on a uniform base that advances by C per tap and 64 per chunk.  Halo: 32-bit byte offsets from the
-        // tile's first halo row (at most C3_BM + 128 rows of C elements: far below 2^32 bytes wherever the pack fits).
-        const unsigned wq = (((unsigned)(n0 + (tid >> 3)) * 9u) * (unsigned)C + (unsigned)(tid & 7) * 8u) * 2u;
-        const size_t wrow = (size_t)32 * 9 * C;                       // elements between a thread's weight rows (uniform)
-        auto load_w0 = [&](unsigned ws, u32x4 (&r)[WCH]) {            // ws = tap * C + cc * 64
-#pragma unroll
-            for (int i = 0; i < WCH; ++i)
-                r[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(wp + ws + i * wrow) + wq);
-        };
-        const int gmb = m0 - W - 1 > 0 ? m0 - W - 1 : 0;
-        const bf16_t* xb = x + (size_t)gmb * C;
-        unsigned xq[XCHK];
-#pragma unroll
-        for (int i = 0; i < XCHK; ++i) {
-            const int px = (tid >> 3) + 32 * i;
-            int gm = m0 - W - 1 + (px < NP ? px : NP - 1);
-            gm = gm < 0 ? 0 : (gm >= M ? M - 1 : gm);
-            xq[i] = ((unsigned)(gm - gmb) * (unsigned)C + (unsigned)(tid & 7) * 8u) * 2u;
-        }
-        auto load_x0 = [&](int cc) {
-#pragma unroll
-            for (int i = 0; i < XCHK; ++i)
-                xr[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(xb + cc * 64) + xq[i]);
-        };
-        bf16_t* sz = sw + 2 * BN * C3_LS;                             // [C3_LS] zeros: what a tap outside the image reads
-        const bf16_t* xl0 = sx + pl[0] * C3_LS + 8 * h;
-        const bf16_t* xl1 = sx + pl[1] * C3_LS + 8 * h;
-        const bf16_t* zl = sz + 8 * h;
-        const bf16_t* bwl = sw + ((wch * CTW) * 32 + c) * C3_LS + 8 * h;
-        // the LDS row of pixel p's fragment at a tap (a constant after unrolling); a lane past M computes a row that
-        // is never written, so the centre tap, which never leaves the image, takes no select
-        auto xrow = [&](const bf16_t* xl, unsigned vm, int tap) -> const bf16_t* {
-            const int kh = tap / 3, kw = tap - 3 * kh;
-            const bf16_t* a = xl + (kh * W + kw) * C3_LS;
-            if (tap == 4) return a;
-            return (vm & (1u << tap)) ? a : zl;
-        };
-        struct Frag {
-            bf16x8 b0, b1, a[CTW];
-        };
-        auto read_frag = [&](Frag& f, const bf16_t* p0, const bf16_t* p1, const bf16_t* bw, int ks) {
-            f.b0 = lds8(p0 + 16 * ks);
-            f.b1 = lds8(p1 + 16 * ks);
-#pragma unroll
-            for (int ct = 0; ct < CTW; ++ct) f.a[ct] = lds8(bw + ct * 32 * C3_LS + 16 * ks);
-        };
-        auto mma_frag = [&](const Frag& f) {
-#pragma unroll
-            for (int ct = 0; ct < CTW; ++ct) {
-                mma16(acc[0][ct], f.a[ct], f.b0);
-                mma16(acc[1][ct], f.a[ct], f.b1);
-            }
-        };
-
-        load_x0(0);
-        load_w0(0u, wr[0]);
-        load_w0((unsigned)C, wr[1]);
-        load_w0(2u * (unsigned)C, wr[2]);
-        store_x();
-        store_w(0, wr[0]);
-        if (tid < C3_LS / 8) reinterpret_cast<u32x4*>(sz)[tid] = u32x4{0u, 0u, 0u, 0u};
-        __syncthreads();
-        Frag fa, fb;                                                  // fa: ks 0 and 2, fb: ks 1 and 3
-        const bf16_t* p0 = xrow(xl0, vmask[0], 0);
-        const bf16_t* p1 = xrow(xl1, vmask[1], 0);
-        read_frag(fa, p0, p1, bwl, 0);
-        for (int cc = 0; cc < nci; ++cc) {
-            const bool more = cc + 1 < nci;
-            const unsigned wsc = (unsigned)cc * 64u, wsn = (unsigned)(more ? cc + 1 : cc) * 64u;   // surplus loads: clamped, never stored
-#pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {                       // 9 = 3 x 3: the register-set rotation closes per chunk
-                // on entry: sw[buf] holds this tap's tile and fa its ks = 0 fragments (in flight); wr[(tap+1) % 3] holds
-                // the next tile, wr[(tap+2) % 3] the one after it (in flight), wr[tap % 3]'s tile is already in LDS
-                const int buf = (cc + tap) & 1;                       // tile cc * 9 + tap
-                const bf16_t* bw = bwl + buf * BN * C3_LS;
-                const bool last = !more && tap == 8;
-                read_frag(fb, p0, p1, bw, 1);
-                if (!last) store_w(buf ^ 1, wr[(tap + 1) % 3]);       // read last before the previous barrier
-                load_w0(tap + 3 < 9 ? wsc + (unsigned)((tap + 3) * C) : wsn + (unsigned)((tap - 6) * C), wr[tap % 3]);
-                if (tap == 4 && more) load_x0(cc + 1);                // next channel chunk's halo flies under taps 4..8
-                __builtin_amdgcn_sched_barrier(0);
-                mma_frag(fa);
-                __builtin_amdgcn_sched_barrier(0);
-                read_frag(fa, p0, p1, bw, 2);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_frag(fb);
-                __builtin_amdgcn_sched_barrier(0);
-                read_frag(fb, p0, p1, bw, 3);
-                __builtin_amdgcn_sched_barrier(0);
-                mma_frag(fa);
-                __builtin_amdgcn_sched_barrier(0);
-                // every wave has read all of this tap's fragments and written the next tile: the barrier sits under
-                // the MFMAs of ks = 3, and so do the first reads of the next tap
+            if (tap == 8 && more) {                               // all waves are done with this halo
+                store_x();
                 lds_barrier();
-                if (tap == 8 && more) {                               // all waves are done with this halo
-                    store_x();
-                    lds_barrier();
-                }
-                if (!last) {
-                    p0 = xrow(xl0, vmask[0], (tap + 1) % 9);
-                    p1 = xrow(xl1, vmask[1], (tap + 1) % 9);
-                    read_frag(fa, p0, p1, bwl + (buf ^ 1) * BN * C3_LS, 0);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-                mma_frag(fb);
-                __builtin_amdgcn_sched_barrier(0);
             }
+            if (!last) {
+                p0 = xrow(xl0, vmask[0], (tap + 1) % 9);
+                p1 = xrow(xl1, vmask[1], (tap + 1) % 9);
+                read_frag(fa, p0, p1, bwl + (buf ^ 1) * BN * C3_LS, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+            mma_frag(fb);
+            __builtin_amdgcn_sched_barrier(0);
         }
     }
     // epilogue: transpose through LDS (all waves share one [128][OS] tile), 16-byte NHWC stores
@@ -1154,7 +1084,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     }
 }
 
-template <int BN, int WPX, int LOOP>
+template <int BN, int WPX>
 int launch_conv3x3(const void* x, const void* wp, void* y, int M, int H, int W, int C, int N, hipStream_t st) {
     constexpr int C3_BM = WPX * 64;
     const int MT = (M + C3_BM - 1) / C3_BM, NT = N / BN;
@@ -1162,30 +1092,20 @@ int launch_conv3x3(const void* x, const void* wp, void* y, int M, int H, int W, 
     size_t sx_elems = (size_t)NP * C3_LS;
     if (sx_elems < (size_t)C3_BM * (BN + 8)) sx_elems = (size_t)C3_BM * (BN + 8);
     sx_elems = (sx_elems + 7) & ~(size_t)7;
-    const size_t lds = (sx_elems + (size_t)2 * BN * C3_LS + (LOOP == 0 ? C3_LS : 0)) * sizeof(bf16_t);   // LOOP 0: the row of zeros
+    const size_t lds = (sx_elems + (size_t)2 * BN * C3_LS + C3_LS) * sizeof(bf16_t);   // halo | two weight tiles | the row of zeros
     if (lds > 160 * 1024) return ADIL_EINVAL;
     if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_kernel<BN, WPX, LOOP>,
+        const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_kernel<BN, WPX>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL((conv3x3_kernel<BN, WPX, LOOP>), dim3((unsigned)(MT * NT)), dim3(256), lds, st, (const bf16_t*)x,
+    hipLaunchKernelGGL((conv3x3_kernel<BN, WPX>), dim3((unsigned)(MT * NT)), dim3(256), lds, st, (const bf16_t*)x,
                        (const bf16_t*)wp, (bf16_t*)y, M, H, W, C, N, MT, NT);
     ADIL_CHECK_LAUNCH();
     return 0;
 }
 
-// adil_conv3x3_loop: which main loop the 3x3 kernels run (0 = unrolled taps and pipelined LDS reads, 1 = the step loop
-// it replaced: the measuring baseline and the bitwise reference).  Read at launch.
-static int g_conv3x3_loop = 0;
-
 }  // namespace
-
-extern "C" int adil_conv3x3_loop(int variant) {
-    const int prev = g_conv3x3_loop;
-    if (variant == 0 || variant == 1) g_conv3x3_loop = variant;
-    return prev;
-}
 
 extern "C" int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream) {
     ADIL_ENTER();
@@ -1194,12 +1114,8 @@ extern "C" int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H
     if (M > 0x7fffffffLL) return ADIL_EINVAL;
     if (9LL * C * N > 0x7fffffffLL) return ADIL_EINVAL;               // weight offsets are 32-bit element indices
     const hipStream_t st = (hipStream_t)stream;
-    if (g_conv3x3_loop == 1) {
-        if (N % 128 == 0) return launch_conv3x3<128, 2, 1>(x, wp, y, (int)M, H, W, C, N, st);
-        return launch_conv3x3<64, 4, 1>(x, wp, y, (int)M, H, W, C, N, st);
-    }
-    if (N % 128 == 0) return launch_conv3x3<128, 2, 0>(x, wp, y, (int)M, H, W, C, N, st);
-    return launch_conv3x3<64, 4, 0>(x, wp, y, (int)M, H, W, C, N, st);   // 64 px x 64 ch wave tiles as well
+    if (N % 128 == 0) return launch_conv3x3<128, 2>(x, wp, y, (int)M, H, W, C, N, st);
+    return launch_conv3x3<64, 4>(x, wp, y, (int)M, H, W, C, N, st);   // 64 px x 64 ch wave tiles as well
 }
 
 // =========================================================================================================== //
@@ -1224,11 +1140,12 @@ namespace {
 
 #define S2_BM 128
 
-// LOOP as in conv3x3_kernel, as far as this loop has the same shape (its taps stay run-time values: the gradient's
-// classes have 4 / 2 / 2 / 1 of them): 0 = per-thread byte offsets computed once (weights 32-bit on a uniform base, source
-// rows plus a uniform tap offset), two fragment register sets and the barrier between the MFMAs of ks = 2 and ks = 3; a
-// finished class then leaves through the buffer whose tile it has just multiplied.  1 = the loop it replaced.  Same bits.
-template <int BN, bool BWD, int LOOP>
+// The main loop is conv3x3_kernel's as far as it has the same shape (the taps stay run-time values: the gradient's classes
+// have 4 / 2 / 2 / 1 of them): per-thread byte offsets computed once (weights 32-bit on a uniform base, source rows plus a
+// uniform tap offset); at BN = 64 two fragment register sets and the barrier between the MFMAs of ks = 2 and ks = 3, a
+// finished class then leaving through the buffer whose tile it has just multiplied; at BN = 128 the second fragment set
+// would spill, so a tap reads its fragments in front of its MFMAs and the barrier closes it.
+template <int BN, bool BWD>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv3x3_s2_kernel(
     const bf16_t* __restrict__ src, const bf16_t* __restrict__ wp, bf16_t* __restrict__ dst, int M, int OH, int OW, int K,
     int NO, int MT, int NT) {
@@ -1238,7 +1155,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     constexpr int OS = BN + 8;
     constexpr int PAIR = (S2_BM + BN) * C3_LS;           // one buffer: source tile [128][C3_LS] | weight tile [BN][C3_LS]
     constexpr int NCLS = BWD ? 4 : 1;
-    constexpr bool PIPE = LOOP == 0 && BN == 64;         // at BN = 128 the second fragment set spills: addresses only
+    constexpr bool PIPE = BN == 64;                      // at BN = 128 the second fragment set spills
     static_assert(S2_BM * OS <= PAIR, "the output transpose goes through one idle buffer");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     bf16_t* sb = reinterpret_cast<bf16_t*>(smem_raw);    // [2][PAIR]
@@ -1282,7 +1199,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     // are multiplied, class after class
     int lcls = 0, lcc = 0, la = 0, lb = 0;
     int lph = cls_ph(0), lpw = cls_pw(0), lnth = BWD ? 1 + lph : 3, lntw = BWD ? 1 + lpw : 3;
-    // LOOP 0: byte offsets, once.  Source: this thread's centre rows; weights: 32 bits (the pack is below 2^31 elements).
+    // byte offsets, once.  Source: this thread's centre rows; weights: 32 bits (the pack is below 2^31 elements).
     size_t sq[XCH];
 #pragma unroll
     for (int i = 0; i < XCH; ++i) sq[i] = ((size_t)ctr[i] * K + (tid & 7) * 8) * sizeof(bf16_t);
@@ -1293,34 +1210,18 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
         const int off = BWD ? (kh == 0 ? OW : 0) + (kw == 0 ? 1 : 0) : (kh - 1) * 2 * OW + (kw - 1);
         const unsigned need = 1u | (kh == 0 ? 2u : 0u) | (kw == 0 ? 4u : 0u);
         unsigned okm = 0;
-        if constexpr (LOOP == 1) {
+        const char* sbase = reinterpret_cast<const char*>(src + lcc * 64);
+        const long long toff = (long long)off * K * (long long)sizeof(bf16_t);   // uniform
 #pragma unroll
-            for (int i = 0; i < XCH; ++i) {
-                const int ch = tid & 7;
-                const bool ok = (flg[i] & need) == need;
-                okm |= ok ? (1u << i) : 0u;
-                const int srow = ok ? ctr[i] + off : ctr[i];                 // always a valid address
-                t.x[i] = *reinterpret_cast<const u32x4*>(src + (size_t)srow * K + lcc * 64 + ch * 8);
-            }
-#pragma unroll
-            for (int i = 0; i < WCH; ++i) {
-                const int q = tid + 256 * i, row = q >> 3, ch = q & 7;
-                t.w[i] = *reinterpret_cast<const u32x4*>(wp + ((size_t)(n0 + row) * 9 + kh * 3 + kw) * K + lcc * 64 + ch * 8);
-            }
-        } else {
-            const char* sbase = reinterpret_cast<const char*>(src + lcc * 64);
-            const long long toff = (long long)off * K * (long long)sizeof(bf16_t);   // uniform
-#pragma unroll
-            for (int i = 0; i < XCH; ++i) {
-                const bool ok = (flg[i] & need) == need;
-                okm |= ok ? (1u << i) : 0u;
-                t.x[i] = *reinterpret_cast<const u32x4*>(sbase + sq[i] + (ok ? toff : 0LL));   // always a valid address
-            }
-            const bf16_t* wbase = wp + (kh * 3 + kw) * K + lcc * 64;
-#pragma unroll
-            for (int i = 0; i < WCH; ++i)
-                t.w[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(wbase + i * wrow) + wq);
+        for (int i = 0; i < XCH; ++i) {
+            const bool ok = (flg[i] & need) == need;
+            okm |= ok ? (1u << i) : 0u;
+            t.x[i] = *reinterpret_cast<const u32x4*>(sbase + sq[i] + (ok ? toff : 0LL));   // always a valid address
         }
+        const bf16_t* wbase = wp + (kh * 3 + kw) * K + lcc * 64;
+#pragma unroll
+        for (int i = 0; i < WCH; ++i)
+            t.w[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(wbase + i * wrow) + wq);
         t.ok = okm;
         if (++lb == lntw) {
             lb = 0;
@@ -1429,7 +1330,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
         lds_barrier();
     };
 
-    // LOOP 0: fa holds the fragments of ks 0 and 2, fb those of ks 1 and 3; the reads of ks + 1 fly under the MFMAs of ks
+    // PIPE: fa holds the fragments of ks 0 and 2, fb those of ks 1 and 3; the reads of ks + 1 fly under the MFMAs of ks
     struct Frag {
         bf16x8 b0, b1, a[CTW];
     };
@@ -1504,25 +1405,19 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void c
     }
 }
 
-template <int BN, bool BWD, int LOOP>
-int launch_conv3x3_s2_loop(const void* src, const void* wp, void* dst, int M, int OH, int OW, int K, int NO, hipStream_t st) {
+template <int BN, bool BWD>
+int launch_conv3x3_s2(const void* src, const void* wp, void* dst, int M, int OH, int OW, int K, int NO, hipStream_t st) {
     const int MT = (M + S2_BM - 1) / S2_BM, NT = NO / BN;
     const size_t lds = (size_t)2 * (S2_BM + BN) * C3_LS * sizeof(bf16_t);
     if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_s2_kernel<BN, BWD, LOOP>,
+        const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_s2_kernel<BN, BWD>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL((conv3x3_s2_kernel<BN, BWD, LOOP>), dim3((unsigned)(MT * NT)), dim3(256), lds, st,
+    hipLaunchKernelGGL((conv3x3_s2_kernel<BN, BWD>), dim3((unsigned)(MT * NT)), dim3(256), lds, st,
                        (const bf16_t*)src, (const bf16_t*)wp, (bf16_t*)dst, M, OH, OW, K, NO, MT, NT);
     ADIL_CHECK_LAUNCH();
     return 0;
-}
-
-template <int BN, bool BWD>
-int launch_conv3x3_s2(const void* src, const void* wp, void* dst, int M, int OH, int OW, int K, int NO, hipStream_t st) {
-    if (g_conv3x3_loop == 1) return launch_conv3x3_s2_loop<BN, BWD, 1>(src, wp, dst, M, OH, OW, K, NO, st);
-    return launch_conv3x3_s2_loop<BN, BWD, 0>(src, wp, dst, M, OH, OW, K, NO, st);
 }
 
 // what both entry points cover; M = rows of the stride-2 grid

@@ -197,182 +197,16 @@ __global__ __launch_bounds__(256) void maxpool_fwd_kernel(const bf16_t* __restri
     *reinterpret_cast<u32x2*>(idx + i * 8) = o;
 }
 
-// maxpool backward (gather form: every conv-output pixel looks at the <= 4 windows that contain it) fused with the
-// ReLU mask (the routed element equals the pooled value p, so [y1 > 0] == [p > 0]: y1 itself is not needed) and
-// the eval-BatchNorm scale.  g_y1 is the gradient wrt the convolution output.
-__global__ __launch_bounds__(256) void stem_pool_bwd_kernel(const bf16_t* __restrict__ g, const uint8_t* __restrict__ idx,
-                                                            const bf16_t* __restrict__ p, const float* __restrict__ scale,
-                                                            bf16_t* __restrict__ gy, int B, int OH, int OW, int PH, int PW,
-                                                            int C8) {
-    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-    const size_t total = (size_t)B * OH * OW * C8;
-    if (i >= total) return;
-    const int c8 = (int)(i % C8);
-    size_t r = i / C8;
-    const int ow = (int)(r % OW); r /= OW;
-    const int oh = (int)(r % OH);
-    const int n = (int)(r / OH);
-    float acc[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] = 0.0f;
-    const int ph0 = oh >> 1, nph = 1 + (oh & 1), pw0 = ow >> 1, npw = 1 + (ow & 1);
-    for (int a = 0; a < nph; ++a) {
-        const int ph = ph0 + a;
-        if (ph >= PH) continue;
-        const int kh = oh - (2 * ph - 1);
-        for (int b = 0; b < npw; ++b) {
-            const int pw = pw0 + b;
-            if (pw >= PW) continue;
-            const unsigned want = (unsigned)(kh * 3 + (ow - (2 * pw - 1)));
-            const size_t at = ((((size_t)n * PH + ph) * PW + pw) * C8 + c8) * 8;
-            const u32x2 id = *reinterpret_cast<const u32x2*>(idx + at);
-            const u32x4 gt = *reinterpret_cast<const u32x4*>(g + at);
-            const u32x4 pt = *reinterpret_cast<const u32x4*>(p + at);
-            float gf[8], pf[8];
-            unpack8(gt, gf);
-            unpack8(pt, pf);
-#pragma unroll
-            for (int j = 0; j < 8; ++j) {
-                const unsigned k = (id[j >> 2] >> (8 * (j & 3))) & 0xffu;
-                acc[j] += (k == want && pf[j] > 0.0f) ? gf[j] : 0.0f;
-            }
-        }
-    }
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[j] *= scale[c8 * 8 + j];
-    *reinterpret_cast<u32x4*>(gy + i * 8) = pack8(acc);
-}
-
 // =========================================================================================================== //
-// stem_conv_bwd: input gradient of the 7x7/2 convolution (64 -> 3 channels), times 1/std of the normalisation.
-//   g_x[ci][ih][iw] = inv_std[ci] * sum_{kh,kw,co} g_y1[(ih+3-kh)/2][(iw+3-kw)/2][co] * w[co][ci][kh][kw]
-//   over the taps with even ih+3-kh, iw+3-kw: the input pixels split into 4 parity classes (ih&1, iw&1) with
-//   3 or 4 taps per axis.  Workgroup = 16 x 32 input pixels of one image = 4 classes x (8 x 16) pixels; wave w takes
-//   sub-rows 2w, 2w+1 of every class.  MFMA roles: A = weights (rows = ci, 3 of 16 used, mfma_16x16x32), B = g_y1 patches
-//   (columns = pixels; 8 consecutive co = one aligned 16-byte LDS read).
-// =========================================================================================================== //
-#define SB_TH 16
-#define SB_TW 32
-#define SB_GR (SB_TH / 2 + 3)          // 11 g_y1 rows
-#define SB_GC (SB_TW / 2 + 3)          // 19 g_y1 columns
-#define SB_PS 72                       // g_y1 pixel stride in LDS (elements): 144 B = 9 x 16 B
-
-// v_mfma_f32_16x16x32_bf16: A lane l -> row l&15, k = 8*(l>>4)+j; B lane l -> column l&15, same k; C register r of
-// lane l -> row 4*(l>>4)+r, column l&15 (layout checked on hardware).  With only 3 useful rows (ci) the 16-row shape
-// wastes half as many MFMA cycles as 32x32x16: 16 pixels x 32 channels of K per instruction, 4 passes.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-template <int A, int BB>
-__device__ __forceinline__ void stem_bwd_class(f32x4 (&acc)[2], const bf16_t* sg, const bf16_t* swb, int w, int l16, int ks) {
-    const int wrow = (l16 < 3 ? l16 : 0) * 49 * 64;
-    const bool wlane = l16 < 3;                            // only 3 of the 16 A rows exist: the other lanes skip the LDS read
-#pragma unroll 1                                           // rolled: a fully unrolled 196-MFMA body hoists LDS reads into spills
-    for (int kh = 1 - A; kh < 7; kh += 2) {
-#pragma unroll
-        for (int kw = 1 - BB; kw < 7; kw += 2) {
-            const int col = l16 + (BB + 3 - kw) / 2 + 1;
-#pragma unroll
-            for (int cg = 0; cg < 2; ++cg) {
-                bf16x8 a = {};
-                if (wlane) a = lds8(swb + wrow + (kh * 7 + kw) * 64 + 32 * cg + 8 * ks);
-#pragma unroll
-                for (int q = 0; q < 2; ++q) {
-                    const int row = 2 * w + q + (A + 3 - kh) / 2 + 1;
-                    const bf16x8 b = lds8(sg + (row * SB_GC + col) * SB_PS + 32 * cg + 8 * ks);
-                    acc[q] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc[q], 0, 0, 0);
-                }
-            }
-        }
-    }
-}
-
-template <typename TX> __device__ __forceinline__ void st_pair(TX* p, float a, float b);
-template <> __device__ __forceinline__ void st_pair<float>(float* p, float a, float b) {
-    *reinterpret_cast<float2*>(p) = make_float2(a, b);
-}
-template <> __device__ __forceinline__ void st_pair<bf16_t>(bf16_t* p, float a, float b) {
-    *reinterpret_cast<unsigned*>(p) = pack2_bf16(a, b);
-}
-
-template <typename TX>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void stem_conv_bwd_kernel(const bf16_t* __restrict__ gy, const bf16_t* __restrict__ wb,
-                                                            StemNorm nm, TX* __restrict__ gx, int H, int W, int OH,
-                                                            int OW) {
-    __shared__ __attribute__((aligned(16))) bf16_t sg[SB_GR * SB_GC * SB_PS];
-    __shared__ __attribute__((aligned(16))) bf16_t swb[3 * 49 * 64];   // the zero row (ci = 3) of w_bwd is never read
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
-    const int n = blockIdx.z, ih0 = blockIdx.y * SB_TH, iw0 = blockIdx.x * SB_TW;
-    {   // weights (3 * 49 * 8 = 1176 chunks) and the g_y1 tile (11 * 19 * 8 = 1672 chunks): every load of a thread is in
-        // flight before the first LDS store (rolled loops paid one memory round trip per chunk: 11 per workgroup)
-        constexpr int NWQ = (3 * 49 * 8 + 255) / 256, NGQ = (SB_GR * SB_GC * 8 + 255) / 256;
-        u32x4 wv[NWQ], gv[NGQ];
-        bool gok[NGQ];
-#pragma unroll
-        for (int j = 0; j < NWQ; ++j) {
-            const int q = tid + 256 * j < 3 * 49 * 8 ? tid + 256 * j : 3 * 49 * 8 - 1;
-            wv[j] = *reinterpret_cast<const u32x4*>(wb + q * 8);
-        }
-        const int ohb = ih0 / 2 - 1, owb = iw0 / 2 - 1;
-#pragma unroll
-        for (int j = 0; j < NGQ; ++j) {
-            const int q = tid + 256 * j < SB_GR * SB_GC * 8 ? tid + 256 * j : SB_GR * SB_GC * 8 - 1;
-            const int ch = q & 7, px = q >> 3;
-            const int row = px / SB_GC, col = px - row * SB_GC;
-            const int oh = ohb + row, ow = owb + col;
-            gok[j] = (oh >= 0) && (oh < OH) && (ow >= 0) && (ow < OW);
-            gv[j] = *reinterpret_cast<const u32x4*>(gy + (((size_t)n * OH + (gok[j] ? oh : 0)) * OW + (gok[j] ? ow : 0)) * 64 + ch * 8);
-        }
-#pragma unroll
-        for (int j = 0; j < NWQ; ++j) {
-            const int q = tid + 256 * j;
-            if (q < 3 * 49 * 8) *reinterpret_cast<u32x4*>(swb + q * 8) = wv[j];
-        }
-#pragma unroll
-        for (int j = 0; j < NGQ; ++j) {
-            const int q = tid + 256 * j;
-            const int ch = q & 7, px = q >> 3;
-            u32x4 t = gv[j];
-            if (!gok[j]) t = u32x4{0u, 0u, 0u, 0u};
-            if (q < SB_GR * SB_GC * 8) *reinterpret_cast<u32x4*>(sg + px * SB_PS + ch * 8) = t;
-        }
-    }
-    lds_sync();
-    const int l16 = lane & 15, ks = lane >> 4;             // pixel column of the class sub-grid / K slice of this lane
-    f32x4 acc[4][2];                                       // [parity class][sub-row 2w + q]
-#pragma unroll
-    for (int k = 0; k < 4; ++k)
-#pragma unroll
-        for (int q = 0; q < 2; ++q) acc[k][q] = f32x4{0.0f, 0.0f, 0.0f, 0.0f};
-    stem_bwd_class<0, 0>(acc[0], sg, swb, w, l16, ks);
-    stem_bwd_class<0, 1>(acc[1], sg, swb, w, l16, ks);
-    stem_bwd_class<1, 0>(acc[2], sg, swb, w, l16, ks);
-    stem_bwd_class<1, 1>(acc[3], sg, swb, w, l16, ks);
-    if (ks == 0) {                                         // accumulator rows 0..2 (= ci) are registers 0..2 of lanes 0..15
-        const int iw = iw0 + 2 * l16;
-#pragma unroll
-        for (int q = 0; q < 2; ++q) {
-#pragma unroll
-            for (int a = 0; a < 2; ++a) {
-                const int ih = ih0 + 2 * (2 * w + q) + a;
-                if (ih < H && iw < W) {
-#pragma unroll
-                    for (int ci = 0; ci < 3; ++ci) {
-                        TX* o = gx + (((size_t)n * 3 + ci) * H + ih) * W + iw;
-                        st_pair<TX>(o, acc[2 * a][q][ci] * nm.inv_std[ci], acc[2 * a + 1][q][ci] * nm.inv_std[ci]);
-                    }
-                }
-            }
-        }
-    }
-}
-
-// =========================================================================================================== //
-// stem_pool_bwd, quad form (adil_stem_bwd_variant 0).  The pooled grid is also the grid of 2 x 2 quads of conv-output
-// pixels (PH = ceil(OH / 2), PW = ceil(OW / 2)): one thread per (n, a, b, 8 channels) loads the four windows (a, b),
-// (a, b+1), (a+1, b), (a+1, b+1) up front — idx, g and p each, clamped and masked at the far edges, 12 loads in flight —
-// and writes the up to four pixels (2a + {0,1}, 2b + {0,1}).  Per element the sum runs over window rows, then window
-// columns, as in the gather form above; a masked window adds +0 to a sum that is never -0, which changes no bit.  A
-// pooled element is fetched by 4 threads, not 9; n and a come from blockIdx (no 64-bit division).
+// stem_pool_bwd, quad form: maxpool backward fused with the ReLU mask (the routed element equals the pooled value p, so
+// [y1 > 0] == [p > 0]: y1 itself is not needed) and the eval-BatchNorm scale.  g_y1 is the gradient wrt the convolution
+// output; a conv-output pixel sums the gradients of the <= 4 windows that contain it and name it as their argmax.
+// The pooled grid is also the grid of 2 x 2 quads of conv-output pixels (PH = ceil(OH / 2), PW = ceil(OW / 2)): one
+// thread per (n, a, b, 8 channels) loads the four windows (a, b), (a, b+1), (a+1, b), (a+1, b+1) up front — idx, g and
+// p each, clamped and masked at the far edges, 12 loads in flight — and writes the up to four pixels (2a + {0,1},
+// 2b + {0,1}).  Per element the sum runs over window rows, then window columns; a masked window adds +0 to a sum that
+// is never -0, which changes no bit.  A pooled element is fetched by 4 threads, not 9; n and a come from blockIdx (no
+// 64-bit division).
 // =========================================================================================================== //
 __global__ __launch_bounds__(256) void stem_pool_bwd_quad_kernel(const bf16_t* __restrict__ g, const uint8_t* __restrict__ idx,
                                                                  const bf16_t* __restrict__ p, const float* __restrict__ scale,
@@ -415,7 +249,7 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_quad_kernel(const bf16_t* _
             pos[k][jj] = okw[k] && pf[jj] > 0.0f;
         }
     }
-    // pixel (2a + dy, 2b + dx): windows in the gather form's order, want = kh * 3 + kw of the pixel inside window k
+    // pixel (2a + dy, 2b + dx): windows by row, then column, want = kh * 3 + kw of the pixel inside window k
     //   (0,0): k0 @ 4          (0,1): k0 @ 5, k1 @ 3          (1,0): k0 @ 7, k2 @ 1          (1,1): k0 @ 8, k1 @ 6, k2 @ 2, k3 @ 0
 #pragma unroll
     for (int dy = 0; dy < 2; ++dy) {
@@ -444,31 +278,53 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_quad_kernel(const bf16_t* _
 }
 
 // =========================================================================================================== //
-// stem_conv_bwd, shift form (adil_stem_bwd_variant 0).  A tap of parity class (A, BB) reads g_y1 at row shift
-// dr = (A + 3 - kh) / 2 and column shift dc = (BB + 3 - kw) / 2, both in {-1, 0, 1, 2}, and for a given (dr, dc) every
-// class has at most one tap: the 49 (class, tap) steps of the class form above are 16 shifts.  The B fragment (g_y1)
-// depends on the shift alone, so the four classes share it and ONE MFMA per (shift, channel half, sub-row):
+// stem_conv_bwd, shift form: input gradient of the 7x7/2 convolution (64 -> 3 channels), times 1/std of the normalisation.
+//   g_x[ci][ih][iw] = inv_std[ci] * sum_{kh,kw,co} g_y1[(ih+3-kh)/2][(iw+3-kw)/2][co] * w[co][ci][kh][kw]
+//   over the taps with even ih+3-kh, iw+3-kw: the input pixels split into 4 parity classes (A, BB) = (ih&1, iw&1) with
+//   3 or 4 taps per axis.  Workgroup = 16 x 32 input pixels of one image = 4 classes x (8 x 16) pixels; wave w takes
+//   sub-rows 2w, 2w+1 of every class.  MFMA roles: A = weights, B = g_y1 patches (columns = pixels; 8 consecutive co =
+//   one aligned 16-byte LDS read).
+// A tap of parity class (A, BB) reads g_y1 at row shift dr = (A + 3 - kh) / 2 and column shift dc = (BB + 3 - kw) / 2,
+// both in {-1, 0, 1, 2}, and for a given (dr, dc) every class has at most one tap: the 49 (class, tap) pairs are 16
+// shifts.  The B fragment (g_y1) depends on the shift alone, so the four classes share it and ONE MFMA per (shift,
+// channel half, sub-row):
 //   A row 4 * class + ci = w[co][ci][A + 3 - 2 dr][BB + 3 - 2 dc], zero where the class has no tap at this shift
 //   (A = 0 with dr = 2, BB = 0 with dc = 2) and for ci = 3; C register r of lane l is row 4 * (l >> 4) + r, so lane group
 //   l >> 4 ends up with class l >> 4, ci in registers 0..2, pixel column l & 15.
-// 64 MFMAs per wave instead of 196, 12 useful rows of 16 instead of 3.  Bits: walking dr = 2, 1, 0, -1 outside,
-// dc = 2, 1, 0, -1 inside, then the channel half, every class meets its own taps in the class form's order (kh, kw
-// ascending, cg) under the same instruction shape; the extra MFMAs have a zero A row and add an exact zero to a sum
-// that started at +0 and so is never -0.  That holds for every finite g_y1: a non-finite g_y1 value turns 0 * inf into
-// NaN at the pixels of the other classes under the same shift (adil_hip.h).
+// 64 MFMAs per wave, 12 useful rows of 16.  Bits: walking dr = 2, 1, 0, -1 outside, dc = 2, 1, 0, -1 inside, then the
+// channel half, every class meets its own taps with kh, then kw ascending (the order of a loop over one class's taps,
+// which tests/golden/retired_variant_bits.json records); the MFMAs of a shift at which a class has no tap have a zero A
+// row there and add an exact zero to a sum that started at +0 and so is never -0.  That holds for every finite g_y1: a
+// non-finite g_y1 value turns 0 * inf into NaN at the pixels of the other classes under the same shift (adil_hip.h).
 // LDS: the g_y1 tile at a pixel stride of 160 B (the 16 lanes that ds_read_b128 serves together — 8 pixels of one K
-//   slice and the other 8 pixels of the next — then fall on 16 different 16-byte bank groups; at the class form's 144 B
-//   this kernel took 335 us instead of 296 at B = 512), and the three weight rows with padded kh and ci strides, so that
-//   the 12 rows x 4 K slices of an A fragment do the same.  52.7 KB: 3 workgroups per CU, as the class form.
-// Grid: the 16 x 32 tile is the class form's, but the launch is one resident set of workgroups (3 per CU) that each walk
-//   a run of consecutive tiles: the weights are staged once per workgroup, not once per tile (18.8 KB next to a 26.8 KB
-//   tile), and the global loads of tile t + 1 are issued in front of the MFMAs of tile t and written to LDS behind them
-//   (one tile per workgroup: 296 us at B = 512; this form: 246 - 262 us).
+//   slice and the other 8 pixels of the next — then fall on 16 different 16-byte bank groups; at 144 B this kernel took
+//   335 us instead of 296 at B = 512), and the three weight rows with padded kh and ci strides, so that the 12 rows x 4
+//   K slices of an A fragment do the same.  52.7 KB: 3 workgroups per CU.
+// Grid: one resident set of workgroups (3 per CU) that each walk a run of consecutive 16 x 32 tiles: the weights are
+//   staged once per workgroup, not once per tile (18.8 KB next to a 26.8 KB tile), and the global loads of tile t + 1
+//   are issued in front of the MFMAs of tile t and written to LDS behind them (one tile per workgroup: 296 us at
+//   B = 512; this form: 246 - 262 us).
 // =========================================================================================================== //
+#define SB_TH 16
+#define SB_TW 32
+#define SB_GR (SB_TH / 2 + 3)          // 11 g_y1 rows
+#define SB_GC (SB_TW / 2 + 3)          // 19 g_y1 columns
 #define SQ_PS 80                       // g_y1 pixel stride (elements): 160 B
 #define SQ_WKH (7 * 64 + 8)            // weight stride of kh (elements): 57 x 16 B
 #define SQ_WCI (7 * SQ_WKH + 24)       // weight stride of ci (elements): 402 x 16 B
 #define SQ_WN (2 * SQ_WCI + 6 * SQ_WKH + 7 * 64)   // weight image, followed by one zero chunk
+
+// v_mfma_f32_16x16x32_bf16: A lane l -> row l&15, k = 8*(l>>4)+j; B lane l -> column l&15, same k; C register r of
+// lane l -> row 4*(l>>4)+r, column l&15 (layout checked on hardware): 16 pixels x 32 channels of K per instruction.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+template <typename TX> __device__ __forceinline__ void st_pair(TX* p, float a, float b);
+template <> __device__ __forceinline__ void st_pair<float>(float* p, float a, float b) {
+    *reinterpret_cast<float2*>(p) = make_float2(a, b);
+}
+template <> __device__ __forceinline__ void st_pair<bf16_t>(bf16_t* p, float a, float b) {
+    *reinterpret_cast<unsigned*>(p) = pack2_bf16(a, b);
+}
 
 template <typename TX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void stem_conv_bwd_shift_kernel(
@@ -483,8 +339,8 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
     int n, ih0, iw0;                                       // the tile being computed
     u32x4 gv[NGQ];                                         // the g_y1 tile on its way from global memory to LDS
     unsigned gok = 0;
-    // every global load of a tile is in flight before the first LDS store, as in the class form; here the loads of tile
-    // t + 1 are issued in front of the MFMAs of tile t and land in LDS behind them
+    // every global load of a tile is in flight before the first LDS store; the loads of tile t + 1 are issued in front
+    // of the MFMAs of tile t and land in LDS behind them
     auto tile_load = [&](int t, int& tn, int& tih0, int& tiw0) {
         const int tx = t % NTX, r = t / NTX;
         tn = r / NTY;
@@ -588,17 +444,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void s
     }
 }
 
-// adil_stem_bwd_variant: which kernels adil_stem_pool_bwd and adil_stem_conv_bwd launch (0 = the quad and shift forms,
-// 1 = the gather and class forms they replaced: the measuring baseline and the bitwise reference).  Read at launch.
-static int g_stem_bwd_variant = 0;
-
 }  // namespace
-
-extern "C" int adil_stem_bwd_variant(int variant) {
-    const int prev = g_stem_bwd_variant;
-    if (variant == 0 || variant == 1) g_stem_bwd_variant = variant;
-    return prev;
-}
 
 // ------------------------------------------------------------------------------------------------------------ //
 extern "C" int adil_stem_conv_fwd(const void* x, int x_dtype, const void* w_fwd, float mean0, float mean1, float mean2,
@@ -638,17 +484,11 @@ extern "C" int adil_stem_pool_bwd(const void* g, const uint8_t* idx, const void*
     ADIL_ENTER();
     if (!g || !idx || !p || !scale || !gy || B <= 0 || OH <= 0 || OW <= 0 || C <= 0 || (C & 7)) return ADIL_EINVAL;
     const int PH = (OH - 1) / 2 + 1, PW = (OW - 1) / 2 + 1;
-    // the quad form takes (n, a) from blockIdx.x and a chunk of (b, c8) from blockIdx.y; grids beyond it keep the gather form
+    // (n, a) is blockIdx.x and a chunk of 256 (b, c8) blockIdx.y: a grid beyond either limit is refused
     const long long rows = (long long)B * PH, cols = ((long long)PW * (C / 8) + 255) / 256;
-    if (g_stem_bwd_variant == 0 && rows <= 0x7fffffffLL && cols <= 65535) {
-        hipLaunchKernelGGL(stem_pool_bwd_quad_kernel, dim3((unsigned)rows, (unsigned)cols), dim3(256), 0, (hipStream_t)stream,
-                           (const bf16_t*)g, idx, (const bf16_t*)p, scale, (bf16_t*)gy, OH, OW, PH, PW, C / 8);
-        ADIL_CHECK_LAUNCH();
-        return 0;
-    }
-    const size_t total = (size_t)B * OH * OW * (C / 8);
-    hipLaunchKernelGGL(stem_pool_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       (const bf16_t*)g, idx, (const bf16_t*)p, scale, (bf16_t*)gy, B, OH, OW, PH, PW, C / 8);
+    if (rows > 0x7fffffffLL || cols > 65535) return ADIL_EINVAL;
+    hipLaunchKernelGGL(stem_pool_bwd_quad_kernel, dim3((unsigned)rows, (unsigned)cols), dim3(256), 0, (hipStream_t)stream,
+                       (const bf16_t*)g, idx, (const bf16_t*)p, scale, (bf16_t*)gy, OH, OW, PH, PW, C / 8);
     ADIL_CHECK_LAUNCH();
     return 0;
 }
@@ -656,33 +496,24 @@ extern "C" int adil_stem_pool_bwd(const void* g, const uint8_t* idx, const void*
 extern "C" int adil_stem_conv_bwd(const void* gy, const void* w_bwd, float inv_std0, float inv_std1, float inv_std2, void* gx,
                                   int gx_dtype, int B, int H, int W, void* stream) {
     ADIL_ENTER();
-    if (!gy || !w_bwd || !gx || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return ADIL_EINVAL;   // B is blockIdx.z
+    if (!gy || !w_bwd || !gx || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return ADIL_EINVAL;   // as the forward
     if (gx_dtype != ADIL_F32 && gx_dtype != ADIL_BF16) return ADIL_EINVAL;
     const StemNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};
     const int OH = H / 2, OW = W / 2;
-    const dim3 grid((W + SB_TW - 1) / SB_TW, (H + SB_TH - 1) / SB_TH, B);
+    const int NTX = (W + SB_TW - 1) / SB_TW, NTY = (H + SB_TH - 1) / SB_TH;
+    const long long ntiles = (long long)NTX * NTY * B;
+    if (ntiles > 0x7fffffffLL) return ADIL_EINVAL;               // the kernel numbers its tiles with 32 bits
     hipStream_t st = (hipStream_t)stream;
-    const long long ntiles = (long long)grid.x * grid.y * B;
-    if (g_stem_bwd_variant == 0 && ntiles <= 0x7fffffffLL) {     // (a tile list beyond 32 bits keeps the class form)
-        // one resident set of workgroups (3 per CU), each walking its share of the tiles: the weights are staged once per
-        // workgroup and the g_y1 loads of a tile run under the MFMAs of the tile before it
-        const long long slots = 3LL * adil_num_cu();
-        const dim3 lin((unsigned)(ntiles < slots ? ntiles : slots));
-        if (gx_dtype == ADIL_F32)
-            hipLaunchKernelGGL(stem_conv_bwd_shift_kernel<float>, lin, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd, nm,
-                               (float*)gx, H, W, OH, OW, (int)grid.x, (int)grid.y, (int)ntiles);
-        else
-            hipLaunchKernelGGL(stem_conv_bwd_shift_kernel<bf16_t>, lin, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd,
-                               nm, (bf16_t*)gx, H, W, OH, OW, (int)grid.x, (int)grid.y, (int)ntiles);
-        ADIL_CHECK_LAUNCH();
-        return 0;
-    }
+    // one resident set of workgroups (3 per CU), each walking its share of the tiles: the weights are staged once per
+    // workgroup and the g_y1 loads of a tile run under the MFMAs of the tile before it
+    const long long slots = 3LL * adil_num_cu();
+    const dim3 lin((unsigned)(ntiles < slots ? ntiles : slots));
     if (gx_dtype == ADIL_F32)
-        hipLaunchKernelGGL(stem_conv_bwd_kernel<float>, grid, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd, nm,
-                           (float*)gx, H, W, OH, OW);
+        hipLaunchKernelGGL(stem_conv_bwd_shift_kernel<float>, lin, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd, nm,
+                           (float*)gx, H, W, OH, OW, NTX, NTY, (int)ntiles);
     else
-        hipLaunchKernelGGL(stem_conv_bwd_kernel<bf16_t>, grid, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd, nm,
-                           (bf16_t*)gx, H, W, OH, OW);
+        hipLaunchKernelGGL(stem_conv_bwd_shift_kernel<bf16_t>, lin, dim3(256), 0, st, (const bf16_t*)gy, (const bf16_t*)w_bwd,
+                           nm, (bf16_t*)gx, H, W, OH, OW, NTX, NTY, (int)ntiles);
     ADIL_CHECK_LAUNCH();
     return 0;
 }

@@ -56,8 +56,9 @@ extern "C" {
  * adil_dense3x3_fwd / adil_dense3x3_bwd after those, and their row-pitch forms adil_dense1x1_fwd_ld / adil_dense1x1_bwd_ld /
  * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those, and adil_bn_pool_head_fwd / adil_bn_pool_head_bwd after those, and
  * adil_attn_max_tokens / adil_attn_fwd / adil_attn_bwd after those: all additive
- * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy / adil_conv3x3_loop / adil_stem_bwd_variant (test and tool entry points: the
- * product calls none of them). */
+ * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls
+ * neither).  adil_conv3x3_loop / adil_stem_bwd_variant were two more of that kind, added under 8 and removed again under 8
+ * with the kernels they selected: library and binding are built from one tree. */
 int adil_abi_version(void);
 
 /* Largest K (atoms) the kernels support. */
@@ -301,8 +302,16 @@ int adil_affine_act_bwd(const void* g, const void* y, const float* scale, void* 
  *                        kh*3+kw of the first maximum (torch.nn.functional.max_pool2d's rule); C % 8 == 0
  *   adil_stem_pool_bwd : gy = route(g; idx) * [p > 0] * scale[c]   (maxpool + ReLU + BatchNorm backward, B x OH x OW x C)
  *   adil_stem_conv_bwd : gx = inv_std[ci] * conv7x7/2 input gradient of gy   (B x 3 x H x W, gx_dtype)
- * The two convolutions take the image index as a grid dimension: 1 <= B <= 65535.  ADIL_EINVAL, before any launch, for a
- * NULL pointer, a non-positive size, odd H or W, B > 65535, a dtype code outside the two, or (pooling) C % 8 != 0.
+ * The two convolutions take 1 <= B <= 65535 (the forward's image index is a grid dimension).  ADIL_EINVAL, before any
+ * launch, for a NULL pointer, a non-positive size, odd H or W, B > 65535, a dtype code outside the two, (pooling)
+ * C % 8 != 0, or a shape beyond the backward kernels' grids, which no image tensor comes near:
+ *   adil_stem_pool_bwd : B * PH > 2^31 - 1 (a row of 2 x 2 pixel quads per workgroup row), or
+ *                        ceil(PW * (C / 8) / 256) > 65535 (the workgroups along such a row)
+ *   adil_stem_conv_bwd : more than 2^31 - 1 tiles of 32 x 16 input pixels, B * ceil(W / 32) * ceil(H / 16)
+ * adil_stem_conv_bwd computes the four input-pixel parity classes (h & 1, w & 1) in one MFMA per (g_y1 shift, channel
+ * half).  For every finite gy that is bit for bit the sum over each class's own taps (kh, then kw ascending).  A
+ * non-finite gy value meets the zero weights of the classes that have no tap at its shift: 0 * inf = NaN then also
+ * reaches input pixels of another parity whose own taps do not read that value.
  * Arithmetic of the pooling pair (restated in tests/stem_pool_reference.py, which the kernels must equal bit for bit):
  *   adil_maxpool_fwd   : the window of (ph, pw) is the taps (kh, kw), scanned in the order kh*3+kw, whose pixel
  *                        (2ph-1+kh, 2pw-1+kw) lies inside the grid; padding taps are ABSENT, not zeros (a window of negative
@@ -322,17 +331,6 @@ int adil_stem_pool_bwd(const void* g, const uint8_t* idx, const void* p, const f
                        int C, void* stream);
 int adil_stem_conv_bwd(const void* gy, const void* w_bwd, float inv_std0, float inv_std1, float inv_std2, void* gx,
                        int gx_dtype, int B, int H, int W, void* stream);
-/* adil_stem_bwd_variant sets which kernels adil_stem_pool_bwd and adil_stem_conv_bwd launch (a host-side int read at
- * launch; 0 = the default: the un-pooling as one thread per 2 x 2 quad of conv-output pixels with its four windows loaded
- * up front, and the 7x7 input gradient as one MFMA per (g_y1 shift, channel half) for all four input-pixel parity classes;
- * 1 = the kernels they replaced — one thread per pixel gathering its windows, one parity class after another — kept as the
- * measuring baseline and the bitwise reference) and returns the previous value; any other argument changes nothing and
- * only returns the current value.  For tests and tools: the product does not call it.
- * Both values give the same bits for every input of adil_stem_pool_bwd, and for every FINITE gy of adil_stem_conv_bwd.
- * Under 0 the four classes share the MFMA, so a non-finite gy value meets the zero weights of the classes that have no
- * tap at its shift: 0 * inf = NaN then also reaches input pixels of another parity whose own taps do not read that value
- * (under 1 those pixels stay finite). */
-int adil_stem_bwd_variant(int variant);
 
 /* Pointwise (1x1) convolution of the frozen network on channels_last storage, with the eval-BatchNorm / residual /
  * ReLU epilogue applied to the accumulators (bf16 in/out, fp32 accumulate):
@@ -369,13 +367,6 @@ int adil_pw_conv_bwd_tile(const void* g, const void* g2, const void* y, const fl
                           void* gres, int M, int K, int N, int relu, const void* xin, const float* pscale,
                           const float* pshift, const void* g3, int sub_w, int sub_hw, void* stream, int bo);
 int adil_pw_route_policy(int policy);
-/* adil_conv3x3_loop sets which main loop adil_conv3x3, adil_conv3x3_s2_fwd and adil_conv3x3_s2_bwd run (a host-side int
- * read at launch; 0 = the default: stride 1, a loop over channel chunks with its 9 taps unrolled and its LDS reads
- * pipelined; stride 2, addresses computed once, and pipelined LDS reads on the 64-channel tile; 1 = the loops over
- * (chunk, tap) steps they replaced, kept as the measuring baseline and the bitwise reference: both give the same bits) and
- * returns the previous value; any other argument changes nothing and only returns the current value.  For tests and
- * tools: the product does not call it. */
-int adil_conv3x3_loop(int variant);
 
 /* Residual join of two consecutive bottlenecks of one stage (conv3 of block i-1 and conv1 of block i) as ONE kernel;
  * the C-channel tensor between the two GEMMs is kept on chip.  W = width in {64, 128}, C = 4 W, M = pixels; bf16

@@ -10,8 +10,7 @@ def short(n):
     n = n.strip('"')
     m0 = re.match(r'(?:void )?(?:\(anonymous namespace\)::)?(\w+_kernel)\b', n)
     if m0 and any(k in m0.group(1) for k in OURS): return m0.group(1)      # "adamw_clamp_kernel" is not a ReLU clamp
-    for key in ('stem_conv_fwd_kernel', 'stem_conv_bwd_kernel', 'stem_conv_bwd_shift_kernel', 'stem_pool_bwd_kernel',
-                'stem_pool_bwd_quad_kernel', 'maxpool_fwd_kernel',
+    for key in ('stem_conv_fwd_kernel', 'stem_conv_bwd_shift_kernel', 'stem_pool_bwd_quad_kernel', 'maxpool_fwd_kernel',
                 'pw_conv_fwd_kernel', 'pw_conv_bwd_kernel', 'conv3x3_kernel'):
         if key in n: return key
     if n.startswith('Cijk_') or 'Cijk_' in n: return 'hipBLASLt GEMM (Cijk_*)'
