@@ -2,8 +2,9 @@
 //   pw_conv_fwd / pw_conv_bwd   1x1 convolutions (stride 1, and the stride-2 downsample ones through an in-kernel
 //                               gather) as GEMMs with the BatchNorm / residual / ReLU epilogue (and
 //                               the previous layer's BatchNorm + ReLU as a prologue) applied on chip, forward and input
-//                               gradient (the gradient at 64 / 128 output channels per workgroup, or at 256 / 512
-//                               in an 8-wave form that prepares its operand once: a measured table picks the tile)
+//                               gradient (both at 64 / 128 output channels per workgroup, or at 256 / 512 in an
+//                               8-wave form that prepares its operand once: a measured table per direction picks the
+//                               tile, and every tile gives the same bits)
 //   pw_join                     conv3 of a bottleneck and conv1 of the next one as one kernel, forward and input
 //                               gradient (the C-channel tensor between them stays on chip)
 //   conv3x3                    3x3 / stride-1 convolutions as an implicit GEMM with linear pixel tiling
@@ -23,7 +24,8 @@
 // activation crosses HBM once.  A library GEMM + a separate epilogue kernel writes and re-reads the pre-activation
 // tensor (the epilogue passes were 10.5 ms of a 51 ms step); here the epilogue runs on the accumulators.
 //   Workgroup = 128 pixels x BN channels (BN = 128 or 64), K in chunks of 64 through LDS (the next chunk waits in
-//   registers: one 37 KB buffer, 3-4 workgroups per CU).
+//   registers: one 37 KB buffer, 3-4 workgroups per CU); or BN = 256 / 512 with 8 waves and double-buffered tiles, one
+//   workgroup per CU (see pw_conv_fwd_kernel).
 //   MFMA roles as in the stem: A = W (rows = channels -> accumulator registers), B = X (columns = pixels -> lanes),
 //   so a lane owns 4 consecutive channels of one pixel per register quad (8-byte residual loads); the finished tile
 //   goes through a per-wave LDS transpose to 16-byte NHWC stores.
@@ -35,19 +37,70 @@ namespace {
 #define PW_LS (PW_BK + 8)              // LDS row stride (elements): 144 B = 9 x 16 B
 #define PW_PK 512                      // most input channels a fused prologue / backward epilogue supports
 
-template <int BN, bool PRO, bool RES>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRO && BN == 128 ? 2 : (RES ? 3 : 4)))) void pw_conv_fwd_kernel(
+// The arithmetic of the prologue and of the epilogue, in ONE place for every tile: the multiply-adds are written as fused
+// operations (what -ffp-contract=fast made of `a * b + c` in the 128 / 64 tiles), so no instantiation is left to contract
+// on its own (FINDINGS.md 31) and every tile rounds at the same points.
+//   prologue: x' = relu(bf16(fma(x, pscale, pshift)))
+__device__ __forceinline__ unsigned pw_fwd_pro2(unsigned x2, f32x2 ps, f32x2 pb) {
+    return relu_bf2(f32x2_to_bf2(__builtin_elementwise_fma(bf2_to_f32x2(x2), ps, pb)));
+}
+//   epilogue of one register quad (4 consecutive channels of one pixel): fma(acc, scale, shift), + res, round, ReLU
+template <bool RES>
+__device__ __forceinline__ u32x2 pw_fwd_epi4(const f32x16& acc, int q, const f32x2* sc, const f32x2* sh, u32x2 r, int relu) {
+    f32x2 v0 = __builtin_elementwise_fma(f32x2{acc[4 * q], acc[4 * q + 1]}, sc[0], sh[0]);
+    f32x2 v1 = __builtin_elementwise_fma(f32x2{acc[4 * q + 2], acc[4 * q + 3]}, sc[1], sh[1]);
+    if (RES) {
+        v0 += bf2_to_f32x2(r[0]);
+        v1 += bf2_to_f32x2(r[1]);
+    }
+    u32x2 t;
+    t[0] = f32x2_to_bf2(v0);
+    t[1] = f32x2_to_bf2(v1);
+    if (relu) { t[0] = relu_bf2(t[0]); t[1] = relu_bf2(t[1]); }
+    return t;
+}
+
+// NW = 4 waves: each owns 32 pixels x BN channels (BN = 64, 128), one LDS buffer, 3 - 4 workgroups per CU.
+//   The conv3 form <128, PRO, RES> is a stream of short workgroups (K <= 512: 1 - 8 chunks, then a 32 KB residual and a
+//   32 KB store each) whose phases overlap only across workgroups, so what it needs is residents: with the residual
+//   held in registers under the whole K loop it took 186 registers = 2 workgroups per CU and ran at 1.9 - 4.3 TB/s;
+//   requested in front of the last chunk's MFMAs instead it takes 154 = 3 per CU: 433 -> 376, 227 -> 207, 156 -> 132 and
+//   119 -> 102 us on the four conv3 shapes of ResNet-50 at B = 512 (FINDINGS.md 43).
+// NW = 8 (the wide tiles, BN = 256 and 512): 4 pixel groups x 2 channel halves, ONE workgroup per CU, so the X chunk is
+// loaded, run through the prologue and written to LDS once for 256 or 512 output channels instead of once per 128.
+//   BN = 256 keeps two buffers of both tiles (2 x 54 KB): one barrier per chunk, chunk i + 1 is written while the waves
+//   that are behind still multiply chunk i, and the loads of chunk i + 2 fly under the MFMAs of chunk i + 1.
+//   BN = 512 (72 KB of W tile) keeps two buffers of the X tile only (2 x 18 KB): the prologue and the X stores of chunk
+//   i + 1 overlap the other waves' MFMAs, the W stores sit between the two barriers.  Its 128 accumulators leave no room
+//   for a residual under the K loop (64 registers): the residual is requested in front of the last chunk's MFMAs.
+// Each output element sees the same MFMA sequence and the same epilogue at every tile: the results are bitwise the same.
+template <int BN, bool PRO, bool RES, int NW>
+__global__ __launch_bounds__(NW * 64)
+__attribute__((amdgpu_waves_per_eu(NW == 8 ? 2 : (PRO && BN == 128 && !RES ? 2 : (RES ? 3 : 4))))) void pw_conv_fwd_kernel(
     const bf16_t* __restrict__ x, const bf16_t* __restrict__ wgt, const float* __restrict__ scale,
     const float* __restrict__ shift, const bf16_t* __restrict__ res, bf16_t* __restrict__ y, int M, int K, int N,
     int relu, int MT, int NT, const float* __restrict__ pscale, const float* __restrict__ pshift, int sub_w, int sub_hw) {
-    constexpr int CT = BN / 32;                          // channel tiles per wave
-    constexpr int XCH = PW_BM * PW_BK / 8 / 256;         // 16-byte chunks of the X tile per thread (4)
-    constexpr int WCH = BN * PW_BK / 8 / 256;            // ... of the W tile (4 or 2)
+    constexpr int NTH = NW * 64;                         // threads
+    constexpr int BW = BN / (NW / 4);                    // channels per wave
+    constexpr int CT = BW / 32;                          // channel tiles per wave
+    constexpr int XCH = PW_BM * PW_BK / 8 / NTH;         // 16-byte chunks of the X tile per thread (4; 2 with 8 waves)
+    constexpr int WCH = BN * PW_BK / 8 / NTH;            // ... of the W tile (2, 4; 4, 8 with 8 waves)
     constexpr int OS = BN + 8;                           // transposed-output pixel stride (elements)
+    constexpr bool DB = NW == 8 && BN == 256;            // two buffers of both tiles
+    constexpr bool DX = NW == 8 && BN == 512;            // two buffers of the X tile, one of the W tile
+    constexpr int XTE = PW_BM * PW_LS;                   // elements of an X tile
+    constexpr int XBS = DB ? (PW_BM + BN) * PW_LS : XTE; // from one X buffer to the other
+    constexpr int WBS = DB ? (PW_BM + BN) * PW_LS : 0;   // from one W buffer to the other
+    // the residual is requested under the last chunk only: where 64 registers of it do not fit (BN = 512), and in the
+    // conv3 form of the 128 tile, where 32 registers less are a third resident workgroup
+    constexpr bool LATE = RES && (CT > 4 || (PRO && BN == 128));
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    bf16_t* sx = reinterpret_cast<bf16_t*>(smem_raw);    // [128][PW_LS]   (single buffer: the next chunk waits in
-    bf16_t* sw = sx + PW_BM * PW_LS;                     // [BN][PW_LS]     registers; 37 KB -> 3-4 workgroups per CU)
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
+    bf16_t* sx = reinterpret_cast<bf16_t*>(smem_raw);    // [128][PW_LS]   (NW = 4: single buffer, the next chunk waits in
+    bf16_t* sw = sx + (DX ? 2 : 1) * XTE;                // [BN][PW_LS]     registers; 37 KB -> 3-4 workgroups per CU)
+    // w = pixel group, wc = channel half.  Spelled per NW: with 4 waves `(tid >> 6) & 3` is not folded to `tid >> 6`, and
+    // the mask alone cost the narrow tiles two more spilled registers and 7 - 15 % of their time on the K >= 256 shapes
+    const int tid = threadIdx.x, lane = tid & 63, w = NW == 8 ? (tid >> 6) & 3 : tid >> 6, wc = NW == 8 ? tid >> 8 : 0;
+    const int c = lane & 31, h = lane >> 5;
     // workgroups are dealt round-robin to the 8 XCDs: consecutive workgroups of ONE XCD share the pixel tile, so the
     // NT reads of an X tile meet in that XCD's L2
     int mt, nt;
@@ -85,7 +138,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRO && BN =
     size_t xrow[XCH];
 #pragma unroll
     for (int i = 0; i < XCH; ++i) {
-        const int id = tid + 256 * i, row = id >> 3;
+        const int id = tid + NTH * i, row = id >> 3;
         const int mm = (m0 + row < M) ? m0 + row : M - 1;
         if (sub_w > 0) {
             const int n = mm / sub_hw, r = mm - n * sub_hw, oh = r / sub_w, ow = r - oh * sub_w;
@@ -98,93 +151,104 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(PRO && BN =
     auto load_tiles = [&](int kc) {
 #pragma unroll
         for (int i = 0; i < XCH; ++i) {
-            const int id = tid + 256 * i, ch = id & 7;
+            const int id = tid + NTH * i, ch = id & 7;
             xr[i] = *reinterpret_cast<const u32x4*>(x + xrow[i] * K + kc * PW_BK + ch * 8);
         }
 #pragma unroll
         for (int i = 0; i < WCH; ++i) {
-            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
+            const int id = tid + NTH * i, row = id >> 3, ch = id & 7;
             wr[i] = *reinterpret_cast<const u32x4*>(wgt + (size_t)(n0 + row) * K + kc * PW_BK + ch * 8);
         }
     };
-    auto store_tiles = [&](int kc) {
+    auto store_x = [&](int kc, int buf) {
 #pragma unroll
         for (int i = 0; i < XCH; ++i) {
-            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
+            const int id = tid + NTH * i, row = id >> 3, ch = id & 7;
             u32x4 t = xr[i];
             if (pro) {
                 const f32x2* ps = reinterpret_cast<const f32x2*>(spro + kc * PW_BK + ch * 8);
                 const f32x2* pb = reinterpret_cast<const f32x2*>(spro + PW_PK + kc * PW_BK + ch * 8);
 #pragma unroll
-                for (int j = 0; j < 4; ++j) t[j] = relu_bf2(f32x2_to_bf2(bf2_to_f32x2(t[j]) * ps[j] + pb[j]));
+                for (int j = 0; j < 4; ++j) t[j] = pw_fwd_pro2(t[j], ps[j], pb[j]);
             }
-            *reinterpret_cast<u32x4*>(sx + row * PW_LS + ch * 8) = t;
+            *reinterpret_cast<u32x4*>(sx + buf * XBS + row * PW_LS + ch * 8) = t;
         }
+    };
+    auto store_w = [&](int buf) {
 #pragma unroll
         for (int i = 0; i < WCH; ++i) {
-            const int id = tid + 256 * i, row = id >> 3, ch = id & 7;
-            *reinterpret_cast<u32x4*>(sw + row * PW_LS + ch * 8) = wr[i];
+            const int id = tid + NTH * i, row = id >> 3, ch = id & 7;
+            *reinterpret_cast<u32x4*>(sw + buf * WBS + row * PW_LS + ch * 8) = wr[i];
         }
     };
 
     load_tiles(0);
-    // the residual does not depend on the GEMM: its loads fly under the whole K loop
+    // the residual does not depend on the GEMM: its loads fly under the whole K loop (LATE: under the last chunk)
     u32x2 rr[RES ? CT : 1][4];
-    if (RES) {
-        const bf16_t* rp = res + (size_t)(mok ? m : M - 1) * N + n0 + 4 * h;
+    auto load_res = [&]() {
+        const bf16_t* rp = res + (size_t)(mok ? m : M - 1) * N + n0 + wc * BW + 4 * h;
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
             for (int q = 0; q < 4; ++q) rr[ct][q] = *reinterpret_cast<const u32x2*>(rp + 32 * ct + 8 * q);
-    }
+    };
+    if (RES && !LATE) load_res();
     f32x16 acc[CT];
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct)
 #pragma unroll
         for (int r = 0; r < 16; ++r) acc[ct][r] = 0.0f;
-    for (int it = 0; it < nk; ++it) {
-        store_tiles(it);
-        if (it + 1 < nk) load_tiles(it + 1);
+    if (DB) {                                            // chunk 0 into buffer 0; from then on chunk it + 1 is written
+        store_x(0, 0);                                   // into the other buffer after the MFMAs of chunk it
+        store_w(0);
+        if (1 < nk) load_tiles(1);
         lds_barrier();
-        const bf16_t* bx = sx + (w * 32 + c) * PW_LS + 8 * h;
-        const bf16_t* bw = sw + c * PW_LS + 8 * h;
+    }
+    if (DX) store_x(0, 0);
+    for (int it = 0; it < nk; ++it) {
+        if (!DB) {
+            if (!DX) store_x(it, 0);
+            store_w(0);
+            if (it + 1 < nk) load_tiles(it + 1);
+            lds_barrier();
+        }
+        if (LATE && it == nk - 1) load_res();
+        const int cur = (DB || DX) ? (it & 1) : 0;
+        const bf16_t* bx = sx + cur * XBS + (w * 32 + c) * PW_LS + 8 * h;
+        const bf16_t* bw = sw + cur * WBS + (wc * BW + c) * PW_LS + 8 * h;
 #pragma unroll
         for (int ks = 0; ks < PW_BK / 16; ++ks) {
             const bf16x8 b = lds8(bx + 16 * ks);
 #pragma unroll
             for (int ct = 0; ct < CT; ++ct) mma16(acc[ct], lds8(bw + ct * 32 * PW_LS + 16 * ks), b);
         }
+        if (DB && it + 1 < nk) {                         // nobody reads buffer cur ^ 1 in this iteration
+            store_x(it + 1, cur ^ 1);
+            store_w(cur ^ 1);
+            if (it + 2 < nk) load_tiles(it + 2);
+        }
+        if (DX && it + 1 < nk) store_x(it + 1, cur ^ 1); // the X half of chunk it + 1; its W half waits for the barrier
         lds_barrier();
     }
-    // epilogue on the accumulators: lane = pixel m, register quad q of tile ct = channels n0 + 32ct + 8q + 4h .. +3
-    bf16_t* so = reinterpret_cast<bf16_t*>(smem_raw) + w * 32 * OS;     // the tile buffers are idle now
+    // epilogue on the accumulators: lane = pixel m, register quad q of tile ct = channels n0 + wc BW + 32ct + 8q + 4h .. +3
+    bf16_t* so = reinterpret_cast<bf16_t*>(smem_raw) + w * 32 * OS + wc * BW;   // the tile buffers are idle now
 #pragma unroll
     for (int ct = 0; ct < CT; ++ct) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int co = 32 * ct + 8 * q + 4 * h;
-            const f32x2* sc = reinterpret_cast<const f32x2*>(ssc + co);
-            const f32x2* sh = reinterpret_cast<const f32x2*>(ssc + BN + co);
-            f32x2 v0 = f32x2{acc[ct][4 * q], acc[ct][4 * q + 1]} * sc[0] + sh[0];
-            f32x2 v1 = f32x2{acc[ct][4 * q + 2], acc[ct][4 * q + 3]} * sc[1] + sh[1];
-            if (RES) {
-                v0 += bf2_to_f32x2(rr[ct][q][0]);
-                v1 += bf2_to_f32x2(rr[ct][q][1]);
-            }
-            u32x2 t;
-            t[0] = f32x2_to_bf2(v0);
-            t[1] = f32x2_to_bf2(v1);
-            if (relu) { t[0] = relu_bf2(t[0]); t[1] = relu_bf2(t[1]); }
-            *reinterpret_cast<u32x2*>(so + c * OS + co) = t;
+            const f32x2* sc = reinterpret_cast<const f32x2*>(ssc + wc * BW + co);
+            const f32x2* sh = reinterpret_cast<const f32x2*>(ssc + BN + wc * BW + co);
+            *reinterpret_cast<u32x2*>(so + c * OS + co) = pw_fwd_epi4<RES>(acc[ct], q, sc, sh, rr[RES ? ct : 0][q], relu);
         }
     }
-    constexpr int CPP = BN / 8;                           // 16-byte chunks per pixel
+    constexpr int CPP = BW / 8;                           // 16-byte chunks per pixel of this wave's corner
 #pragma unroll
     for (int i = 0; i < 32 * CPP / 64; ++i) {
         const int id = lane + 64 * i, px = id / CPP, ch = id - px * CPP;
         const u32x4 t = *reinterpret_cast<const u32x4*>(so + px * OS + ch * 8);
         const int mm = m0 + w * 32 + px;
-        if (mm < M) *reinterpret_cast<u32x4*>(y + (size_t)mm * N + n0 + ch * 8) = t;
+        if (mm < M) *reinterpret_cast<u32x4*>(y + (size_t)mm * N + n0 + wc * BW + ch * 8) = t;
     }
 }
 
@@ -405,28 +469,35 @@ int launch_pw_bwd(const void* g, const void* g2, const void* y, const float* sca
 template <int BN, bool PRO, bool RES>
 int launch_pw_fwd_r(const void* x, const void* w, const float* scale, const float* shift, const void* res, void* y, int M,
                   int K, int N, int relu, const float* pscale, const float* pshift, int sub_w, int sub_hw, hipStream_t st) {
+    constexpr int NW = BN >= 256 ? 8 : 4;
     const int MT = (M + PW_BM - 1) / PW_BM, NT = N / BN;
-    const size_t tiles = (size_t)(PW_BM + BN) * PW_LS * sizeof(bf16_t);
+    // BN = 256: two buffers of both tiles; BN = 512: two X tiles and one W tile (108 KB either way)
+    const size_t tiles = (size_t)(BN == 256 ? 2 * (PW_BM + BN) : (BN == 512 ? 2 * PW_BM + BN : PW_BM + BN)) * PW_LS * sizeof(bf16_t);
     const size_t outb = (size_t)4 * 32 * (BN + 8) * sizeof(bf16_t);
-    const size_t lds = tiles > outb ? tiles : outb;
+    const size_t lds = tiles > outb ? tiles : outb;      // BN = 512: 130 KB for the output transpose
     if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)pw_conv_fwd_kernel<BN, PRO, RES>,
+        const hipError_t e = hipFuncSetAttribute((const void*)pw_conv_fwd_kernel<BN, PRO, RES, NW>,
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) return (int)e;
     }
-    hipLaunchKernelGGL((pw_conv_fwd_kernel<BN, PRO, RES>), dim3((unsigned)(MT * NT)), dim3(256), lds, st, (const bf16_t*)x,
+    hipLaunchKernelGGL((pw_conv_fwd_kernel<BN, PRO, RES, NW>), dim3((unsigned)(MT * NT)), dim3(NW * 64), lds, st, (const bf16_t*)x,
                        (const bf16_t*)w, scale, shift, (const bf16_t*)res, (bf16_t*)y, M, K, N, relu, MT, NT, pscale, pshift, sub_w, sub_hw);
     ADIL_CHECK_LAUNCH();
     return 0;
 }
 
-template <int BN, bool PRO>
+template <int BN>
 int launch_pw_fwd(const void* x, const void* w, const float* scale, const float* shift, const void* res, void* y, int M,
                   int K, int N, int relu, const float* pscale, const float* pshift, int sub_w, int sub_hw, hipStream_t st) {
-    // without a residual the 32 registers of its prefetch are free: 4 workgroups per CU instead of 3
+    // without a residual the 32 registers of its prefetch are free: 4 workgroups per CU instead of 3 (narrow tiles)
+    if (pscale != nullptr) {
+        if (res != nullptr)
+            return launch_pw_fwd_r<BN, true, true>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+        return launch_pw_fwd_r<BN, true, false>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+    }
     if (res != nullptr)
-        return launch_pw_fwd_r<BN, PRO, true>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
-    return launch_pw_fwd_r<BN, PRO, false>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+        return launch_pw_fwd_r<BN, false, true>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+    return launch_pw_fwd_r<BN, false, false>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
 }
 
 }  // namespace
@@ -526,21 +597,71 @@ extern "C" int adil_pw_route_policy(int policy) {
     return prev;
 }
 
+// The forward tile BN under the same policy: 0 = the table below, 1 = the narrow tiles (128, or 64 where N % 128)
+// everywhere, 2 = the widest tile that divides N (512, 256) wherever one does.  The table follows the rule of kPwWide:
+// a row is in it only where the wide tile's median beat the narrow tile's median by more than the narrow tile's own
+// max - min over five alternating rounds, it names the faster of the two wide tiles, and its M bounds are the measured
+// pixel counts (tools/bench_pw_fwd.py at --batch 512, 256, 128 and 64: profiles/pw_fwd_bench.json and
+// pw_fwd_bench_b{256,128,64}.json), from the smallest to the largest one that passed, open above where B = 512 did.
+// Unlike the gradient, the forward narrow tile is not short of residents (3 - 4 workgroups per CU, 600 - 790 TFLOP/s on
+// the long-K shapes at B = 512), and a wide tile is ONE workgroup per CU whose load, MFMA and store phases overlap with
+// nobody's: it wins where the narrow grid no longer fills the CUs (small M) or K is long enough to hide its ends
+// (K = 2048), and loses 10 - 35 % on every conv3 shape (K <= 512, N = 4 K) at B >= 256.
+struct PwFwdWideRow { int K, N, m_lo, m_hi, bn; };
+static const PwFwdWideRow kPwFwdWide[] = {
+    {2048, 512, 12544, INT32_MAX, 256},    // layer4 conv1:        84 -> 77 us at B = 512 (512: 85), 47 -> 39 at 256; 34 -> 37 at 128
+    {1024, 256, 25088, 50176, 256},        // layer3 conv1:        48 -> 46 us at B = 256, 29 -> 25 at 128; 81 -> 95 at 512
+    {1024, 512, 12544, 12544, 256},        // layer4.0 conv1:      29 -> 24 us at B = 64; 49 -> 47 at 128 is inside the spread
+    {1024, 2048, 3136, 3136, 256},         // layer4.0 downsample: 29 -> 25 us at B = 64
+    {512, 1024, 12544, 12544, 512},        // layer3.0 downsample: 29.8 -> 29.2 us at B = 64 (256: 30.7)
+    {512, 2048, 6272, 6272, 512},          // layer4 conv3:        36.4 -> 35.8 us at B = 128 (256: 36.9)
+    {512, 2048, 3136, 3136, 256},          //                      21.5 -> 20.5 us at B = 64 (512: 33.8)
+};
+
+static int pw_fwd_tile(int M, int K, int N) {
+    const int narrow = (N % 128 == 0) ? 128 : 64;
+    if (N % 256 || g_pw_route_policy == 1) return narrow;
+    if (g_pw_route_policy == 2) return (N % 512 == 0) ? 512 : 256;
+    for (const PwFwdWideRow& r : kPwFwdWide)
+        if (r.K == K && r.N == N && M >= r.m_lo && M <= r.m_hi) return r.bn;
+    return narrow;
+}
+
+static int pw_fwd_check(const void* x, const void* w, const float* scale, const float* shift, void* y, int M, int K, int N,
+                        const float* pscale, const float* pshift, int sub_w, int sub_hw) {
+    if (!x || !w || !scale || !shift || !y || M <= 0 || K <= 0 || N <= 0 || (K % PW_BK) || (N % 64)) return ADIL_EINVAL;
+    if ((pscale != nullptr) != (pshift != nullptr) || (pscale && K > PW_PK)) return ADIL_EINVAL;
+    if (sub_w < 0 || (sub_w > 0 && (sub_hw <= 0 || sub_hw % sub_w || M % sub_hw))) return ADIL_EINVAL;
+    return 0;
+}
+
+static int pw_fwd_run(int bn, const void* x, const void* w, const float* scale, const float* shift, const void* res, void* y,
+                      int M, int K, int N, int relu, const float* pscale, const float* pshift, int sub_w, int sub_hw,
+                      hipStream_t st) {
+    if (bn == 512) return launch_pw_fwd<512>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+    if (bn == 256) return launch_pw_fwd<256>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+    if (bn == 128) return launch_pw_fwd<128>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+    return launch_pw_fwd<64>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+}
+
 extern "C" int adil_pw_conv_fwd(const void* x, const void* w, const float* scale, const float* shift, const void* res,
                                 void* y, int M, int K, int N, int relu, const float* pscale, const float* pshift,
                                 int sub_w, int sub_hw, void* stream) {
     ADIL_ENTER();
-    if (!x || !w || !scale || !shift || !y || M <= 0 || K <= 0 || N <= 0 || (K % PW_BK) || (N % 64)) return ADIL_EINVAL;
-    if ((pscale != nullptr) != (pshift != nullptr) || (pscale && K > PW_PK)) return ADIL_EINVAL;
-    if (sub_w < 0 || (sub_w > 0 && (sub_hw <= 0 || sub_hw % sub_w || M % sub_hw))) return ADIL_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    if (pscale) {
-        if (N % 128 == 0)
-            return launch_pw_fwd<128, true>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
-        return launch_pw_fwd<64, true>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
-    }
-    if (N % 128 == 0) return launch_pw_fwd<128, false>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
-    return launch_pw_fwd<64, false>(x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, st);
+    const int rc = pw_fwd_check(x, w, scale, shift, y, M, K, N, pscale, pshift, sub_w, sub_hw);
+    if (rc) return rc;
+    return pw_fwd_run(pw_fwd_tile(M, K, N), x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw,
+                      (hipStream_t)stream);
+}
+
+extern "C" int adil_pw_conv_fwd_tile(const void* x, const void* w, const float* scale, const float* shift, const void* res,
+                                     void* y, int M, int K, int N, int relu, const float* pscale, const float* pshift,
+                                     int sub_w, int sub_hw, void* stream, int bn) {
+    ADIL_ENTER();
+    const int rc = pw_fwd_check(x, w, scale, shift, y, M, K, N, pscale, pshift, sub_w, sub_hw);
+    if (rc) return rc;
+    if ((bn != 64 && bn != 128 && bn != 256 && bn != 512) || N % bn) return ADIL_EINVAL;
+    return pw_fwd_run(bn, x, w, scale, shift, res, y, M, K, N, relu, pscale, pshift, sub_w, sub_hw, (hipStream_t)stream);
 }
 
 // =========================================================================================================== //

@@ -57,7 +57,7 @@ extern "C" {
  * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those, and adil_bn_pool_head_fwd / adil_bn_pool_head_bwd after those, and
  * adil_attn_max_tokens / adil_attn_fwd / adil_attn_bwd after those: all additive
  * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls
- * neither).  adil_conv3x3_loop / adil_stem_bwd_variant were two more of that kind, added under 8 and removed again under 8
+ * neither), and adil_pw_conv_fwd_tile after them.  adil_conv3x3_loop / adil_stem_bwd_variant were two more of that kind, added under 8 and removed again under 8
  * with the kernels they selected: library and binding are built from one tree. */
 int adil_abi_version(void);
 
@@ -367,6 +367,13 @@ int adil_pw_conv_bwd_tile(const void* g, const void* g2, const void* y, const fl
                           void* gres, int M, int K, int N, int relu, const void* xin, const float* pscale,
                           const float* pshift, const void* g3, int sub_w, int sub_hw, void* stream, int bo);
 int adil_pw_route_policy(int policy);
+/* adil_pw_conv_fwd picks its output-channel tile the same way (64, 128, or the wide 256 / 512 of an 8-wave form that
+ * stages the x operand once per workgroup) from K, N and M, under the same adil_pw_route_policy (2 = the widest tile
+ * dividing N); every tile gives the same bits.  adil_pw_conv_fwd_tile is the same call at the forced tile `bn`, for tests
+ * and tools: bn outside {64, 128, 256, 512} or N % bn != 0: ADIL_EINVAL before any launch, y untouched. */
+int adil_pw_conv_fwd_tile(const void* x, const void* w, const float* scale, const float* shift, const void* res, void* y,
+                          int M, int K, int N, int relu, const float* pscale, const float* pshift, int sub_w, int sub_hw,
+                          void* stream, int bn);
 
 /* Residual join of two consecutive bottlenecks of one stage (conv3 of block i-1 and conv1 of block i) as ONE kernel;
  * the C-channel tensor between the two GEMMs is kept on chip.  W = width in {64, 128}, C = 4 W, M = pixels; bf16
