@@ -135,7 +135,7 @@ class Out(NamedTuple):
 
 def finish(ar, o):
     """The output tensor (values, in the arithmetic's dtype) of an Out."""
-    v = ar.rnd(o.pre) if o.dtype == BF16 else o.pre.float().to(o.pre.dtype)
+    v = ar.rnd(o.pre) if o.dtype == BF16 else ar.f32(o.pre).to(o.pre.dtype)
     if o.relu:
         v = torch.where(v > 0, v, torch.zeros_like(v))
     if o.mask is not None:
@@ -431,9 +431,9 @@ def stem_fwd(ar, x, w, mean, inv_std, scale, shift):
     dt = ar.dtype
     B, _, H, W = x.shape
     OH, OW = H // 2, W // 2
-    mean = torch.tensor(mean, dtype=F32, device=x.device).view(1, 3, 1, 1)
-    istd = torch.tensor(inv_std, dtype=F32, device=x.device).view(1, 3, 1, 1)
-    xn = ar.rnd((x.float() - mean) * istd).to(dt)
+    mean = ar.f32(torch.tensor(mean, dtype=F64, device=x.device)).view(1, 3, 1, 1)     # fp32 arguments (the doubles over `Unrounded`)
+    istd = ar.f32(torch.tensor(inv_std, dtype=F64, device=x.device)).view(1, 3, 1, 1)
+    xn = ar.rnd((ar.f32(x) - mean) * istd).to(dt)
     cols = F.unfold(xn, 7, padding=3, stride=2)                        # [B][3*49][OH*OW], rows (ci, kh, kw)
     cols = cols.view(B, 3, 49, OH * OW).permute(0, 3, 2, 1).reshape(B * OH * OW, 147)     # (kh, kw, ci): the kernel's K order
     wk = w.to(dt).permute(0, 2, 3, 1).reshape(64, 147)
@@ -449,7 +449,7 @@ def stem_bwd(ar, gy, w, inv_std, H, W, out_dtype):
     B, OH, OW, _ = gy.shape
     wk = w.to(dt).reshape(64, 147)                                     # columns (ci, kh, kw): F.fold's order
     gs = gy.to(dt).reshape(B, OH * OW, 64)
-    istd = torch.tensor(inv_std, dtype=F32, device=gy.device).to(dt).view(1, 3, 1, 1)     # the kernel takes fp32 arguments
+    istd = ar.f32(torch.tensor(inv_std, dtype=F64, device=gy.device)).to(dt).view(1, 3, 1, 1)   # the kernel takes fp32 arguments
     cols = ar.mm(gs.reshape(-1, 64), wk).reshape(B, OH * OW, 147).transpose(1, 2)
     acc = F.fold(cols, (H, W), 7, padding=3, stride=2) + 0.0
     S = None

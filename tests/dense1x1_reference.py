@@ -120,9 +120,9 @@ def expected(o):
 
 def prologue(ar, x, pscale, pshift):
     """(pre, a) in fp32, as specified: pre = fadd(fmul(f32(x), pscale), pshift), a = bf16(max(pre, 0)), <= 0 -> +0."""
-    x32, ps, pb = x.float(), pscale.float(), pshift.float()
+    x32, ps, pb = ar.f32(x), ar.f32(pscale), ar.f32(pshift)           # fp32 registers (the real values over `Unrounded`)
     if "fma" in ar.mut:                                                # mutant: the prologue contracted to one fma
-        pre = (x32.double() * ps.double() + pb.double()).float()
+        pre = ar.f32(x32.double() * ps.double() + pb.double())
     elif "no_pshift" in ar.mut:                                        # mutant: pshift dropped
         pre = x32 * ps
     else:

@@ -133,9 +133,9 @@ def operands(name, leg, B, HW, C, N):
 # ------------------------------------------------------------------------------------------------------------ operations
 def pre_of(ar, x, pscale, pshift):
     """fp32 on both sides: f32(f32(x * pscale) + pshift).  Mutants: one fma; the shift left out."""
-    x32, ps, pb = x.float(), pscale.float().to(x.device), pshift.float().to(x.device)
+    x32, ps, pb = ar.f32(x), ar.f32(pscale).to(x.device), ar.f32(pshift).to(x.device)   # the real values over `Unrounded`
     if "fma" in ar.mut:                                                 # the product is not rounded
-        return (x32.double() * ps.double() + pb.double()).float()
+        return ar.f32(x32.double() * ps.double() + pb.double())
     if "shift_ignored" in ar.mut:
         return x32 * ps
     return x32 * ps + pb
@@ -162,7 +162,7 @@ def post_of(ar, pre):
 def pooled_of(ar, p, HW):
     """pooled [B][C] fp32 and (reference) S, sum |p| in fp64."""
     S, Sabs = href.pool_sum(ar, p)
-    pooled = href.scale_f32(S, HW)
+    pooled = href.scale_f32(S, HW, ar)
     if "relu_after_pool" in ar.mut:
         pooled = torch.where(pooled > 0, pooled, torch.zeros_like(pooled))
     return pooled, S, Sabs
@@ -171,16 +171,17 @@ def pooled_of(ar, p, HW):
 def gx_of(ar, gpooled, x, pscale, pshift):
     """[B][HW][C] bf16 from the STORED fp32 gpooled: two fp32 multiplies in the specified order, one rounding, the mask."""
     HW = x.shape[1]
-    ps = pscale.float().to(gpooled.device)
+    ps = ar.f32(pscale).to(gpooled.device)
     if "no_pscale_in_gx" in ar.mut:
-        v = href.scale_f32(gpooled, HW)
+        v = href.scale_f32(gpooled, HW, ar)
     elif "scale_before_inv_hw" in ar.mut:
-        v = href.scale_f32(gpooled.float() * ps, HW)
+        v = href.scale_f32(ar.f32(gpooled) * ps, HW, ar)
     else:
-        v = href.scale_f32(gpooled, HW) * ps
-    v = ar.rnd(v).bfloat16()
+        v = href.scale_f32(gpooled, HW, ar) * ps
+    v = ar.rnd(v)
+    v = v if isinstance(ar, href.Unrounded) else v.bfloat16()          # over `Unrounded` alone: the real product
     m = mask_of(ar, x, pre_of(ar, x, pscale, pshift))
-    return torch.where(m, v[:, None, :].expand(m.shape), torch.zeros((), dtype=BF16, device=v.device)).contiguous()
+    return torch.where(m, v[:, None, :].expand(m.shape), torch.zeros((), dtype=v.dtype, device=v.device)).contiguous()
 
 
 def emulate(op, mut=()):

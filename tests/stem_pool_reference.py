@@ -138,12 +138,12 @@ class GyRef(NamedTuple):
     S: torch.Tensor              # sum |terms|
     n: torch.Tensor              # number of non-zero terms
     q: torch.Tensor              # smallest bf16 ulp among the non-zero terms (inf where there is none)
-    scale: torch.Tensor          # fp32 [C]
+    scale: torch.Tensor          # fp32 [C] (fp64 as handed in: an unrounded reference)
 
     @property
     def want(self):
         """bf16_rne(f32(f32(sum) * scale)) as fp32 values."""
-        return bf16_rne(self.sum.float() * self.scale.float())
+        return gy_of(Arith(), self)
 
     @property
     def exact_sum(self):
@@ -156,6 +156,11 @@ class GyRef(NamedTuple):
         sc = self.scale.double().abs()
         A = 4 * 2.0 ** -24 * self.S * sc
         return 2.0 ** -8 * ((self.sum * self.scale.double()).abs() + A) + A
+
+
+def gy_of(ar, ref):
+    """gy of a GyRef in the arithmetic `ar`: rnd(f32(f32(sum) * scale)); over `Unrounded` the real product."""
+    return ar.rnd(ar.f32(ar.f32(ref.sum) * ar.f32(ref.scale)))
 
 
 def bf16_ulp(v):
@@ -184,7 +189,7 @@ def pool_bwd(g, idx, p, scale, OH, OW):
     q = torch.full((n_el,), float("inf"), dtype=F64, device=dev)
     q = q.scatter_reduce(0, flat[nz], bf16_ulp(t[nz]), "amin")
     shape = (B, OH, OW, C)
-    return GyRef(s.view(shape), S.view(shape), n.view(shape), q.view(shape), scale.float())
+    return GyRef(s.view(shape), S.view(shape), n.view(shape), q.view(shape), scale if scale.dtype == F64 else scale.float())
 
 
 MUTANTS_FWD = ("ge", "start_at_zero", "nan_loses", "idx_transposed", "origin_2ph", "next_image")
