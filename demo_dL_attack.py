@@ -65,55 +65,9 @@ def build_parser():
     p.add_argument('--own-strided-conv', type=int, default=0, choices=[0, 1],
                    help='with --fast-classifier: 1 = the stride-2 3x3 convolutions of the ResNet run in the hand-written '
                         'kernel too (no library convolution is left in the classifier); 0 (default) = the library')
-    p.add_argument('--own-depthwise', type=int, default=0, choices=[0, 1],
-                   help='-m mobilenet --dtype bf16: 1 = the 17 depthwise 3x3 layers (with their BatchNorm and ReLU6) run in '
-                        'the hand-written kernel on channels_last storage; 0 (default) = the library.  Ignored otherwise')
-    p.add_argument('--own-pointwise', type=int, default=0, choices=[0, 1],
-                   help='-m mobilenet --dtype bf16: 1 = the 34 1x1 layers (with their BatchNorm, ReLU6 and residual add) run '
-                        'in the narrow-channel GEMM kernel on channels_last storage; 0 (default) = the library.  Independent '
-                        'of --own-depthwise.  Ignored otherwise')
-    p.add_argument('--own-dense-pointwise', type=int, default=0, choices=[0, 1],
-                   help='-m densenet --dtype bf16: 1 = the 61 pre-activated 1x1 layers (58 dense layers, 3 transitions, with the '
-                        'BatchNorm + ReLU in front and behind) run in the pre-activated pointwise kernels on channels_last '
-                        'storage; 0 (default) = the library.  Ignored otherwise')
-    p.add_argument('--own-dense-conv', type=int, default=0, choices=[0, 1],
-                   help='-m densenet --dtype bf16: 1 = the 58 3x3 growth convolutions 128 -> 32 run in the 32-channel 3x3 '
-                        'kernels on channels_last storage; 0 (default) = the library.  Independent of --own-dense-pointwise; '
-                        'with both only the 7x7 stem is left to the library.  Ignored otherwise')
-    p.add_argument('--own-dense-block', type=int, default=0, choices=[0, 1],
-                   help='-m densenet --dtype bf16: 1 = each of the 4 dense blocks runs on one channels_last feature buffer '
-                        '(no torch.cat, input gradients accumulated inside the 1x1 gradient kernel); needs '
-                        '--own-dense-pointwise 1 and --own-dense-conv 1; 0 (default) = per-layer tensors.  Ignored otherwise')
-    p.add_argument('--own-dense-transition', type=int, default=0, choices=[0, 1],
-                   help='-m densenet --dtype bf16: 1 = each of the 3 transitions runs as one kernel that pools in front of '
-                        'the 1x1 convolution (a quarter of the GEMM, no full-resolution intermediate); needs '
-                        '--own-dense-pointwise 1; 0 (default) = the 1x1 kernel and the library pool.  Ignored otherwise')
-    p.add_argument('--own-dense-stem', type=int, default=0, choices=[0, 1],
-                   help='-m densenet --dtype bf16: 1 = the normalisation and conv0 / norm0 / relu0 / pool0 run in the stem '
-                        'kernels on the attack\'s own tensors; 0 (default) = the library.  Independent of the other dense '
-                        'switches; with all five no library convolution or pooling is left in the trunk.  Ignored otherwise')
-    p.add_argument('--own-dense-head', default='0', choices=['0', 'inference', 'always'],
-                   help='-m densenet --dtype bf16: norm5 + ReLU + global pooling + classifier in the pooled-head kernels with '
-                        'a BatchNorm + ReLU prologue and fp32 logits on channels_last storage; inference = only inside the '
-                        'DDrague inference loop (engine.precise_head), always = in every classifier call; 0 (default) = the '
-                        'library BatchNorm, ReLU, pooling and bf16 linear layer.  Independent of the other dense switches; '
-                        'with all six no library call is left in the classifier.  Ignored otherwise')
-    p.add_argument('--own-first-conv', type=int, default=0, choices=[0, 1],
-                   help='-m mobilenet --dtype bf16: 1 = the normalisation and the 3 -> 32 first convolution (with its BatchNorm '
-                        'and ReLU6) run in the first-convolution kernels on the attack\'s own tensors; 0 (default) = the '
-                        'library.  Independent of the other two; with all three no library convolution is left.  Ignored '
-                        'otherwise')
-    p.add_argument('--own-head', default='0', choices=['0', 'inference', 'always'],
-                   help='-m mobilenet --dtype bf16: global pooling + the last linear layer in the pooled-head kernels with '
-                        'fp32 logits on channels_last storage; inference = only inside the DDrague inference loop '
-                        '(engine.precise_head), always = in every classifier call; 0 (default) = the library pooling and '
-                        'bf16 linear layer.  Independent of the other three; with all four no library call is left in the '
-                        'classifier.  Ignored otherwise')
-    p.add_argument('--own-attention', type=int, default=0, choices=[0, 1],
-                   help='-m vit --dtype bf16: 1 = the self-attention between the in-projection and the out-projection of the '
-                        '12 encoder blocks runs in the whole-head attention kernels (no score matrix, softmax or permuted '
-                        'copy is written); 0 (default) = plain library matmuls and softmax.  The projections, the MLP, '
-                        'LayerNorm and GELU stay on the library.  Ignored otherwise')
+    zoo.add_switch_arguments(p.add_argument_group(
+        'kernel switches', 'Each belongs to one network and needs --dtype bf16; it is ignored otherwise.  A switch that '
+                           'needs channels_last storage makes the network channels_last.'))
     return p
 
 
@@ -157,7 +111,6 @@ def main(args):
 
     model_name = args.model.lower()          # names the dictionary file, as upstream (demo_dL_attack.py:41, adil.py:89-91)
     dtype = torch.bfloat16 if args.dtype == 'bf16' else torch.float32
-    fast = bool(args.fast_classifier) and dtype == torch.bfloat16 and zoo.canonical_name(model_name).startswith('resnet')
 
     structured = bool(args.synthetic and args.synthetic_structured)
     if args.synthetic:
@@ -173,35 +126,8 @@ def main(args):
     weights = args.weights
     if structured and weights is None:
         weights = _fitted_weights(model_name, args.seed, train_dataset, n_classes, device)
-    mobile_bf16 = dtype == torch.bfloat16 and zoo.canonical_name(model_name) == 'mobilenet_v2'
-    own_dw, own_pw = bool(args.own_depthwise) and mobile_bf16, bool(args.own_pointwise) and mobile_bf16
-    own_fc = bool(args.own_first_conv) and mobile_bf16
-    own_head = {'0': False, 'inference': 'inference', 'always': True}[args.own_head] if mobile_bf16 else False
-    own_dense = (bool(args.own_dense_pointwise) and dtype == torch.bfloat16
-                 and zoo.canonical_name(model_name) == 'densenet121')
-    own_dense_conv = (bool(args.own_dense_conv) and dtype == torch.bfloat16
-                      and zoo.canonical_name(model_name) == 'densenet121')
-    own_dense_block = (bool(args.own_dense_block) and dtype == torch.bfloat16
-                       and zoo.canonical_name(model_name) == 'densenet121')
-    own_dense_transition = (bool(args.own_dense_transition) and dtype == torch.bfloat16
-                            and zoo.canonical_name(model_name) == 'densenet121')
-    own_dense_stem = (bool(args.own_dense_stem) and dtype == torch.bfloat16
-                      and zoo.canonical_name(model_name) == 'densenet121')
-    own_dense_head = ({'0': False, 'inference': 'inference', 'always': True}[args.own_dense_head]
-                      if dtype == torch.bfloat16 and zoo.canonical_name(model_name) == 'densenet121' else False)
-    own_attention = (bool(args.own_attention) and dtype == torch.bfloat16
-                     and zoo.canonical_name(model_name) == 'vit_b_16')
     model = zoo.build_classifier(model_name, seed=args.seed, weights=weights, device=device, dtype=dtype,
-                                 channels_last=(fast or own_dw or own_pw or own_fc or bool(own_head) or own_dense
-                                                or own_dense_conv or own_dense_stem or bool(own_dense_head)),
-                                 own_dense_head=own_dense_head, own_attention=own_attention,
-                                 own_dense_transition=own_dense_transition, own_dense_stem=own_dense_stem,
-                                 own_depthwise=own_dw, own_pointwise=own_pw, own_dense_pointwise=own_dense,
-                                 own_dense_conv=own_dense_conv, own_dense_block=own_dense_block,
-                                 own_first_conv=own_fc, fuse_bn_act=fast,
-                                 fuse_stem=fast,
-                                 head_fp32="inference" if fast else own_head,   # fp32 logits inside the DDrague inference loop
-                                 own_strided_conv=fast and bool(args.own_strided_conv))
+                                 **classifier_keywords(args, model_name, dtype))
     if args.clean_accuracy:                                                               # demo_dL_attack.py:65-66
         from model_accuracy import model_accuracy, model_accuracy_distributed
         dataset.indexed = False
@@ -237,6 +163,17 @@ def main(args):
     if writer:                                                                            # demo_dL_attack.py:153-156
         torch.save(test_perf, os.path.join(out_dir, 'model_adil_resultat_test_ce.bin'))
     return val_perf, test_perf
+
+
+def classifier_keywords(args, model_name, dtype):
+    """What the flags ask of zoo.build_classifier: --fast-classifier (bf16 ResNets: the FusedResNet path with the fused
+    stem and fp32 logits inside the DDrague inference loop) and the rows of zoo.SWITCHES."""
+    fast = bool(args.fast_classifier) and dtype == torch.bfloat16 and zoo.canonical_name(model_name).startswith('resnet')
+    kw, needs_channels_last = zoo.switch_keywords(args, zoo.SWITCHES, model_name, dtype)
+    if fast:
+        kw['head_fp32'] = "inference"
+    return dict(kw, channels_last=fast or needs_channels_last, fuse_bn_act=fast, fuse_stem=fast,
+                own_strided_conv=fast and bool(args.own_strided_conv))
 
 
 def _fitted_weights(model_name, seed, train_dataset, n_classes, device):

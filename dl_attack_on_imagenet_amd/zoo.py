@@ -10,7 +10,7 @@ are randomly initialised from a seed (synthetic throughput / plumbing runs).
 from __future__ import annotations
 
 from collections import OrderedDict
-from typing import NamedTuple, Optional
+from typing import Callable, NamedTuple, Optional, Tuple
 
 import torch
 import torch.nn as nn
@@ -32,6 +32,20 @@ class Normalize(nn.Module):
         mean = self.mean.reshape(1, 3, 1, 1).to(input.dtype)
         std = self.std.reshape(1, 3, 1, 1).to(input.dtype)
         return (input - mean) / std
+
+
+class _PreciseHead:
+    """The `precise_head` protocol that engine.precise_head looks for, for networks with a switchable fp32 head: `head32`
+    is the head module or None, `head32_on` says whether forward goes through it (both set by the network's __init__ and
+    by whatever attaches the head).  List it in front of nn.Module."""
+
+    def precise_head(self, enabled: bool) -> bool:
+        """Switch the fp32 head on / off (networks whose head was attached in "inference" mode); returns the previous
+        state.  Without a head nothing changes."""
+        prev = self.head32_on
+        if self.head32 is not None:
+            self.head32_on = bool(enabled)
+        return prev
 
 
 # ----------------------------------------------------------------------------- ResNet
@@ -140,7 +154,7 @@ class _DenseBlock(nn.ModuleDict):
         return torch.cat(feats, 1)
 
 
-class DenseNet(nn.Module):
+class DenseNet(_PreciseHead, nn.Module):
     def __init__(self, block_config=(6, 12, 24, 16), growth=32, init_features=64, num_classes=1000):
         super().__init__()
         feats = OrderedDict([('conv0', nn.Conv2d(3, init_features, 7, 2, 3, bias=False)),
@@ -172,14 +186,6 @@ class DenseNet(nn.Module):
             return self.head32(x)
         x = F.relu(self.features(x), inplace=True)
         return self.classifier(torch.flatten(F.adaptive_avg_pool2d(x, 1), 1))
-
-    def precise_head(self, enabled: bool) -> bool:
-        """Switch the fp32 head on / off (networks rewritten by use_own_dense_head_(net, "inference")); returns the
-        previous state.  The protocol of `FusedResNet.precise_head`, which is what engine.precise_head looks for."""
-        prev = self.head32_on
-        if self.head32 is not None:
-            self.head32_on = bool(enabled)
-        return prev
 
 
 # ----------------------------------------------------------------------------- ViT-B/16
@@ -284,7 +290,7 @@ class _InvertedResidual(nn.Module):
         return x + self.conv(x) if self.use_res else self.conv(x)
 
 
-class MobileNetV2(nn.Module):
+class MobileNetV2(_PreciseHead, nn.Module):
     def __init__(self, num_classes=1000):
         super().__init__()
         cfg = [(1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2), (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1)]
@@ -305,14 +311,6 @@ class MobileNetV2(nn.Module):
             return self.head32(x)
         x = F.adaptive_avg_pool2d(x, 1)
         return self.classifier(torch.flatten(x, 1))
-
-    def precise_head(self, enabled: bool) -> bool:
-        """Switch the fp32 head on / off (networks rewritten by use_own_head_(net, "inference")); returns the previous
-        state.  The protocol of `FusedResNet.precise_head`, which is what engine.precise_head looks for."""
-        prev = self.head32_on
-        if self.head32 is not None:
-            self.head32_on = bool(enabled)
-        return prev
 
 
 class VGG11(nn.Module):
@@ -1335,13 +1333,16 @@ class _Fp32Head(_KeepsFp32):
     fp32 bits (`_KeepsFp32`), the pooled features are widened before the layer, the logits come out fp32.
     Why (round 4, VERDICT r3 #1c): a bf16 head rounds logits of magnitude 16-64 to steps of 0.125-0.25, which is the scale
     on which the attack's argmax decisions ("fooled") and its margin loss are taken; the head is 2 MFLOP per image next to
-    the backbone's 4 GFLOP, so keeping it fp32 costs nothing measurable.  The backbone stays bf16."""
+    the backbone's 4 GFLOP, so keeping it fp32 costs nothing measurable.  The backbone stays bf16.
+    `persistent`: whether `weight` / `bias` are state_dict entries (FusedResNet's head) or not (the heads attached to a
+    network that keeps its Linear)."""
     _KEEP_FP32 = ('weight', 'bias')
 
-    def __init__(self, fc: nn.Linear):
+    def __init__(self, fc: nn.Linear, persistent: bool = True):
         super().__init__()
-        self.register_buffer('weight', fc.weight.detach().float().clone())
-        self.register_buffer('bias', fc.bias.detach().float().clone() if fc.bias is not None else torch.zeros(fc.out_features))
+        self.register_buffer('weight', fc.weight.detach().float().clone(), persistent=persistent)
+        bias = fc.bias.detach().float().clone() if fc.bias is not None else torch.zeros(fc.out_features)
+        self.register_buffer('bias', bias, persistent=persistent)
 
     def forward(self, x):
         return F.linear(x.float().mean(dim=(2, 3)), self.weight, self.bias)
@@ -1357,9 +1358,7 @@ class _OwnHead(_Fp32Head):
     _KEEP_FP32 = ('weight', 'bias', 'wt')
 
     def __init__(self, fc: nn.Linear):
-        super().__init__(fc)
-        for name in ('weight', 'bias'):                  # `_Fp32Head` registered them as persistent buffers
-            self.register_buffer(name, getattr(self, name), persistent=False)
+        super().__init__(fc, persistent=False)
         self.register_buffer('wt', self.weight.t().contiguous(), persistent=False)
 
     def forward(self, x):
@@ -1369,13 +1368,17 @@ class _OwnHead(_Fp32Head):
         return super().forward(x)
 
 
+def _check_head_mode(mode, head: str) -> None:
+    if mode not in (True, "inference"):
+        raise ValueError(f"the {head}'s mode must be True or 'inference'")
+
+
 def use_own_head_(net: nn.Module, mode=True) -> int:
     """Attach an `_OwnHead` built from the last Linear of a MobileNetV2 (after its weights are loaded) and route the
     network's forward through it: `mode` True = always, "inference" = only while `precise_head(True)` is in force
     (engine.precise_head, the DDrague inference solver).  `classifier` stays in place under its names and serves the
     network whenever the head is off.  Returns how many heads were attached (1)."""
-    if mode not in (True, "inference"):
-        raise ValueError("the own head's mode must be True or 'inference'")
+    _check_head_mode(mode, "own head")
     if not isinstance(net, MobileNetV2) or not isinstance(net.classifier[-1], nn.Linear):
         raise ValueError("the own head rewrites the pooling + classifier of MobileNetV2")
     net.head32 = _OwnHead(net.classifier[-1])
@@ -1395,9 +1398,7 @@ class _OwnDenseHead(_Fp32Head):
     _KEEP_FP32 = ('weight', 'bias', 'wt', 'pscale', 'pshift')
 
     def __init__(self, bn: nn.BatchNorm2d, fc: nn.Linear):
-        super().__init__(fc)
-        for name in ('weight', 'bias'):                  # `_Fp32Head` registered them as persistent buffers
-            self.register_buffer(name, getattr(self, name), persistent=False)
+        super().__init__(fc, persistent=False)
         self.register_buffer('wt', self.weight.t().contiguous(), persistent=False)
         pscale, pshift = _bn_affine(bn)
         self.register_buffer('pscale', pscale, persistent=False)
@@ -1423,8 +1424,7 @@ def use_own_dense_head_(net: nn.Module, mode=True) -> int:
     and route the network's forward through it: `mode` True = always, "inference" = only while `precise_head(True)` is in
     force (engine.precise_head, the DDrague inference solver).  `norm5` and `classifier` stay in place under their names
     and serve the network whenever the head is off.  Returns how many heads were attached (1)."""
-    if mode not in (True, "inference"):
-        raise ValueError("the own dense head's mode must be True or 'inference'")
+    _check_head_mode(mode, "own dense head")
     if not _has_dense_head(net):
         raise ValueError("the own dense head rewrites norm5 + ReLU + pooling + classifier of a DenseNet (features ending in "
                          "a BatchNorm2d named norm5, a Linear classifier)")
@@ -1448,7 +1448,7 @@ def use_own_attention_(net: nn.Module) -> int:
     return n
 
 
-class FusedResNet(nn.Module):
+class FusedResNet(_PreciseHead, nn.Module):
     """A frozen ResNet whose BatchNorm(eval) / residual add / ReLU run as ONE elementwise kernel per convolution
     (`ops.affine_act`, forward and input-gradient backward) instead of 2-3 separate PyTorch kernels.  Convolution
     weights are untouched; the function is the original network's (up to one rounding per activation).  GPU only.
@@ -1511,13 +1511,6 @@ class FusedResNet(nn.Module):
             return self.head32(x)
         return self.fc(torch.flatten(self.avgpool(x), 1))
 
-    def precise_head(self, enabled: bool) -> bool:
-        """Switch the fp32 head on / off (networks built with head_fp32="inference"); returns the previous state."""
-        prev = self.head32_on
-        if self.head32 is not None:
-            self.head32_on = bool(enabled)
-        return prev
-
 
 @torch.no_grad()
 def fit_centroid_head(model: nn.Module, images: torch.Tensor, labels: torch.Tensor, classes: int, device,
@@ -1559,6 +1552,115 @@ def fit_centroid_head(model: nn.Module, images: torch.Tensor, labels: torch.Tens
     return top2[:, 0] - top2[:, 1], out.argmax(1)
 
 
+# ----------------------------------------------------------------------------- the kernel switches
+class Switch(NamedTuple):
+    """One kernel switch of `build_classifier`: a keyword there and a flag of the CLIs."""
+    keyword: str                    # build_classifier's keyword
+    flag: str                       # the CLI flag; its dest is the flag with underscores
+    network: str                    # the canonical network it belongs to
+    kernels: str                    # what its kernels are called in the error texts
+    apply: Callable                 # use_own_*_(net[, mean, std][, value]), called after the weights are loaded
+    help: str                       # one sentence, for the docstring and for --help
+    bf16: bool = True               # needs a bfloat16 network
+    channels_last: bool = True      # needs channels_last=True
+    requires: Tuple[str, ...] = ()  # keywords that must be on as well
+    three_state: bool = False       # False / True / "inference" (CLI: 0 / always / inference) instead of off / on
+    normalises: bool = False        # takes over the input normalisation: the Sequential then holds the network alone
+
+    @property
+    def dest(self) -> str:
+        return self.flag.lstrip('-').replace('-', '_')
+
+
+NETWORK_LABELS = {'mobilenet_v2': 'MobileNetV2', 'densenet121': 'DenseNet-121', 'vit_b_16': 'ViT-B/16'}
+
+# In the order they are applied (a row that `requires` others comes behind them).  A new switch is one row here and its
+# use_own_*_ function; build_classifier's keyword of the same name is the only other line.
+SWITCHES = (
+    Switch('own_depthwise', '--own-depthwise', 'mobilenet_v2', 'depthwise', use_own_depthwise_,
+           'the 17 depthwise 3x3 layers with their BatchNorm and ReLU6 run in the depthwise kernels (`_OwnDepthwise`)'),
+    Switch('own_pointwise', '--own-pointwise', 'mobilenet_v2', 'pointwise', use_own_pointwise_,
+           'the 34 1x1 layers with their BatchNorm, ReLU6 and residual add run in the narrow-channel GEMM kernels '
+           '(`_OwnPointwise`, `_OwnInvertedResidual`)'),
+    Switch('own_first_conv', '--own-first-conv', 'mobilenet_v2', 'first-convolution', use_own_first_conv_,
+           'the normalisation and the 3 -> 32 first convolution with its BatchNorm and ReLU6 run in the first-convolution '
+           'kernels on the attack\'s own tensors (`_OwnFirstConv`)', normalises=True),
+    Switch('own_dense_pointwise', '--own-dense-pointwise', 'densenet121', 'pre-activated pointwise',
+           use_own_dense_pointwise_,
+           'the 61 pre-activated 1x1 layers (58 dense layers, 3 transitions) with the BatchNorm + ReLU in front and behind '
+           'run in the pre-activated pointwise kernels (`_OwnDenseLayer`, `_OwnTransition`)'),
+    Switch('own_dense_conv', '--own-dense-conv', 'densenet121', '32-channel 3x3', use_own_dense_conv_,
+           'the 58 3x3 growth convolutions 128 -> 32 run in the 32-channel 3x3 kernels (`_OwnGrowthConv`)'),
+    Switch('own_dense_block', '--own-dense-block', 'densenet121', 'dense-block', use_own_dense_block_,
+           'each of the 4 dense blocks runs on one channels_last feature buffer: no torch.cat, input gradients accumulated '
+           'inside the 1x1 gradient kernel (`_OwnDenseBlock`)', requires=('own_dense_pointwise', 'own_dense_conv')),
+    Switch('own_dense_transition', '--own-dense-transition', 'densenet121', 'transition', use_own_dense_transition_,
+           'each of the 3 transitions runs as one kernel that pools in front of the 1x1 convolution '
+           '(`ops.dense_transition`)', requires=('own_dense_pointwise',)),
+    Switch('own_dense_stem', '--own-dense-stem', 'densenet121', 'stem', use_own_dense_stem_,
+           'the normalisation and conv0 / norm0 / relu0 / pool0 run in the stem kernels on the attack\'s own tensors '
+           '(`_OwnDenseStem`)', normalises=True),
+    Switch('head_fp32', '--own-head', 'mobilenet_v2', 'head', use_own_head_,
+           'global pooling + the last linear layer run in the pooled-head kernels with fp32 logits (`_OwnHead`)',
+           three_state=True),
+    Switch('own_dense_head', '--own-dense-head', 'densenet121', 'head', use_own_dense_head_,
+           'norm5 + ReLU + global pooling + classifier run in the pooled-head kernels with a BatchNorm + ReLU prologue and '
+           'fp32 logits (`_OwnDenseHead`)', three_state=True),
+    Switch('own_attention', '--own-attention', 'vit_b_16', 'attention', use_own_attention_,
+           'the self-attention between the in-projection and the out-projection of the 12 encoder blocks runs in the '
+           'whole-head attention kernels; the projections, the MLP, LayerNorm and GELU stay on the library',
+           channels_last=False),
+)
+_SWITCH = {row.keyword: row for row in SWITCHES}
+
+
+def _check_switch(row: Switch, values: dict, key: str, dtype, channels_last: bool) -> None:
+    """One row's conditions, in the order value, network, required switches, bf16, channels_last."""
+    kw, value = row.keyword, values[row.keyword]
+    if row.three_state and value not in (False, True, "inference"):
+        raise ValueError(f"{kw} must be False, True or 'inference'")
+    if not value:
+        return
+    if key != row.network:
+        raise ValueError(f"{kw} is a switch of {NETWORK_LABELS[row.network]} (the {row.kernels} kernels are wired into no "
+                         f"other network)")
+    if not all(values[r] for r in row.requires):
+        raise ValueError(f"{kw} needs {' and '.join(r + '=True' for r in row.requires)} (it works on what they rewrite)")
+    if row.bf16 and dtype != torch.bfloat16:
+        raise ValueError(f"{kw} needs a bfloat16 network (the {row.kernels} kernels work on bf16 activations)")
+    if row.channels_last and not channels_last:
+        raise ValueError(f"{kw} needs channels_last=True (the {row.kernels} kernels work on channels_last storage)")
+
+
+def add_switch_arguments(parser, rows=SWITCHES) -> None:
+    """The CLI flags of `rows`: 0 / 1 for a two-state row, 0 / inference / always for a three-state one, off by default."""
+    for row in rows:
+        text = f"{NETWORK_LABELS[row.network]}: {row.help}"
+        if row.requires:
+            text += "; needs " + " and ".join(f"{_SWITCH[r].flag} 1" for r in row.requires)
+        if row.three_state:
+            text += "; inference = only inside the DDrague inference loop (engine.precise_head), always = in every call"
+            parser.add_argument(row.flag, default='0', choices=['0', 'inference', 'always'],
+                                help=text + "; 0 (default) = the library.  Ignored on other networks")
+        else:
+            parser.add_argument(row.flag, type=int, default=0, choices=[0, 1],
+                                help=text + "; 0 (default) = the library.  Ignored on other networks")
+
+
+def switch_keywords(args, rows, name: str, dtype):
+    """`build_classifier`'s keywords for `rows` from parsed CLI arguments, and whether any active one needs channels_last.
+    A flag counts only on its row's network, and in bf16 where the row needs that; otherwise the switch is off."""
+    key, kw, needs_cl = canonical_name(name), {}, False
+    for row in rows:
+        value = getattr(args, row.dest)
+        value = {'0': False, 'inference': 'inference', 'always': True}[value] if row.three_state else bool(value)
+        if key != row.network or (row.bf16 and dtype != torch.bfloat16):
+            value = False
+        kw[row.keyword] = value
+        needs_cl |= bool(value) and row.channels_last
+    return kw, needs_cl
+
+
 def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights: Optional[str] = None,
                      device=None, dtype: torch.dtype = torch.float32, channels_last: bool = False,
                      fold_bn: bool = False, pad_input_channels: int = 0, fuse_bn_act: bool = False,
@@ -1568,110 +1670,31 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      own_dense_conv: bool = False, own_dense_block: bool = False,
                      own_dense_transition: bool = False, own_dense_stem: bool = False,
                      own_dense_head=False, own_attention: bool = False) -> nn.Module:
-    """Sequential(Normalize, net), eval mode, parameters frozen — the object both CLIs hand to ADIL.
-    fold_bn / pad_input_channels / fuse_bn_act / fuse_stem apply the function-preserving rewrites above (off by
-    default); fuse_bn_act (ResNets, GPU only) supersedes fold_bn; fuse_stem (with fuse_bn_act, bf16 only) moves the
-    normalisation and the first stage into the stem kernels (the Sequential then holds the network alone); head_fp32
-    (with fuse_bn_act, or MobileNetV2 in bf16 + channels_last, where it is the pooled-head kernel pair of `_OwnHead`,
-    independent of the three own_* switches) keeps global pooling + the last linear layer in fp32 under a bf16 cast (fp32
-    logits): True = always, "inference" = only inside engine.precise_head (the DDrague inference solver), see FusedResNet;
-    own_strided_conv (with fuse_bn_act) runs the stride-2 3x3 convolutions in the hand-written kernel instead of the
-    library (off by default);
-    own_depthwise (MobileNetV2, bf16, channels_last) runs the 17 depthwise 3x3 layers with their BatchNorm and ReLU6 in
-    the hand-written kernel (`_OwnDepthwise`; off by default); own_pointwise (same conditions, independent of
-    own_depthwise) runs the 34 1x1 layers with their BatchNorm, ReLU6 and residual add in the narrow-channel GEMM kernel
-    (`_OwnPointwise` / `_OwnInvertedResidual`; off by default); own_first_conv (same conditions, independent of the other
-    two) moves the normalisation and the 3 -> 32 first convolution with its BatchNorm and ReLU6 into the first-convolution
-    kernels (`_OwnFirstConv`; the Sequential then holds the network alone, as with fuse_stem; off by default);
-    own_dense_pointwise (DenseNet-121, bf16, channels_last) runs the 61 pre-activated 1x1 layers (58 dense layers, 3
-    transitions) with the BatchNorm + ReLU in front and behind in the pre-activated pointwise kernels (`_OwnDenseLayer` /
-    `_OwnTransition`; off by default); own_dense_conv (same conditions, independent of own_dense_pointwise) runs the 58
-    3x3 growth convolutions 128 -> 32 in the 32-channel 3x3 kernels (`_OwnGrowthConv`; off by default).  With both on, the
-    7x7 stem is the only library convolution left in DenseNet-121; own_dense_block (needs BOTH of them, hence their
-    conditions) runs each of the 4 dense blocks on one channels_last feature buffer: the 3x3 kernels write their 32
-    channels straight into it, the 1x1 kernels read a prefix of it in place, and the input gradients are accumulated in
-    one gradient buffer inside the 1x1 gradient kernel (`_OwnDenseBlock`, `ops.dense_block`; no torch.cat and no
-    gradient-sum kernels inside a block; off by default); own_dense_transition (needs own_dense_pointwise, independent of
-    the other two) runs each of the 3 transitions as one kernel that pools in front of the 1x1 convolution
-    (`use_own_dense_transition_`, `ops.dense_transition`; off by default); own_dense_stem (DenseNet-121, bf16,
-    channels_last, independent of the others) moves the normalisation and conv0 / norm0 / relu0 / pool0 into the stem
-    kernels (`_OwnDenseStem`; the Sequential then holds the network alone, as with fuse_stem; off by default);
-    own_dense_head (DenseNet-121, bf16, channels_last, independent of the other five) runs norm5 + ReLU + global pooling +
-    classifier in the pooled-head kernels with the BatchNorm + ReLU prologue and gives fp32 logits (`_OwnDenseHead`,
-    `ops.bn_pool_head`): True = in every call, "inference" = only inside engine.precise_head (the DDrague inference
-    solver; the learner keeps the library head and bf16 logits), as head_fp32 does for MobileNetV2; head_fp32 itself
-    stays a switch of the other networks; off by default.  With all six switches no library call is left in
-    DenseNet-121;
-    own_attention (ViT-B/16, bf16; channels_last is not needed: the tokens are rows) runs the segment between the
-    in-projection and the out-projection of the 12 encoder blocks in the whole-head attention kernels
-    (`use_own_attention_`, `ops.attention`; the projections, the MLP, LayerNorm and GELU stay on the library; off by
-    default)."""
+    """Sequential(Normalize, net), eval mode, parameters frozen: the object both CLIs hand to ADIL.  Everything below is
+    a function-preserving rewrite, off by default, applied after the weights are loaded.
+    fold_bn folds every BatchNorm into its convolution; pad_input_channels zero-pads the first convolution's input.
+    fuse_bn_act (ResNets, GPU only; supersedes fold_bn) builds a `FusedResNet`, and three more keywords are its
+    constructor's: fuse_stem (bf16 only) moves the normalisation and the first stage into the stem kernels, head_fp32
+    keeps global pooling + the last linear layer in fp32 (True = always, "inference" = only inside engine.precise_head),
+    own_strided_conv runs the stride-2 3x3 convolutions in the hand-written kernel; see `FusedResNet`.
+    Every other keyword is a row of `SWITCHES`, which says what it needs (its network, bf16, channels_last, other
+    switches) and what it does; on MobileNetV2 head_fp32 is such a row.  A switch that is on where it cannot work is a
+    ValueError, never a silent fall-back.  Where a stem is fused (fuse_stem or a row that normalises) the Sequential
+    holds the network alone."""
+    given = locals()
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
-    own_head = bool(head_fp32) and key == 'mobilenet_v2'
-    if head_fp32 and not fuse_bn_act and not own_head:
+    values = {row.keyword: given[row.keyword] for row in SWITCHES}
+    if key != _SWITCH['head_fp32'].network:              # elsewhere head_fp32 is FusedResNet's argument, not the row
+        values['head_fp32'] = False
+    if head_fp32 and not fuse_bn_act and not values['head_fp32']:
         raise ValueError("head_fp32 is a switch of the FusedResNet path (fuse_bn_act=True) and of MobileNetV2")
-    if own_head and dtype != torch.bfloat16:
-        raise ValueError("head_fp32 needs a bfloat16 network (the head kernels work on bf16 activations)")
-    if own_head and not channels_last:
-        raise ValueError("head_fp32 needs channels_last=True (the head kernels work on channels_last storage)")
+    _check_switch(_SWITCH['head_fp32'], values, key, dtype, channels_last)    # with the other head_fp32 checks, as ever
     if own_strided_conv and not fuse_bn_act:
         raise ValueError("own_strided_conv is a switch of the FusedResNet path (fuse_bn_act=True)")
-    for switch, on, kernels, layers in (('own_depthwise', own_depthwise, 'depthwise', 'the depthwise 3x3 layers'),
-                                        ('own_pointwise', own_pointwise, 'pointwise', 'the 1x1 layers'),
-                                        ('own_first_conv', own_first_conv, 'first-convolution', 'the first convolution')):
-        if on and key != 'mobilenet_v2':
-            raise ValueError(f"{switch} is a switch of MobileNetV2 (no other network has {layers} rewritten)")
-        if on and dtype != torch.bfloat16:
-            raise ValueError(f"{switch} needs a bfloat16 network (the {kernels} kernels work on bf16 activations)")
-        if on and not channels_last:
-            raise ValueError(f"{switch} needs channels_last=True (the {kernels} kernels work on channels_last storage)")
-    if own_dense_pointwise and key != 'densenet121':
-        raise ValueError("own_dense_pointwise is a switch of DenseNet-121 (no other network has the pre-activated 1x1 layers "
-                         "rewritten)")
-    if own_dense_pointwise and dtype != torch.bfloat16:
-        raise ValueError("own_dense_pointwise needs a bfloat16 network (the pre-activated pointwise kernels work on bf16 "
-                         "activations)")
-    if own_dense_pointwise and not channels_last:
-        raise ValueError("own_dense_pointwise needs channels_last=True (the pre-activated pointwise kernels work on "
-                         "channels_last storage)")
-    if own_dense_conv and key != 'densenet121':
-        raise ValueError("own_dense_conv is a switch of DenseNet-121 (no other network has the growth convolutions "
-                         "rewritten)")
-    if own_dense_conv and dtype != torch.bfloat16:
-        raise ValueError("own_dense_conv needs a bfloat16 network (the 32-channel 3x3 kernels work on bf16 activations)")
-    if own_dense_conv and not channels_last:
-        raise ValueError("own_dense_conv needs channels_last=True (the 32-channel 3x3 kernels work on channels_last "
-                         "storage)")
-    if own_dense_block and key != 'densenet121':
-        raise ValueError("own_dense_block is a switch of DenseNet-121 (no other network has dense blocks)")
-    if own_dense_block and not (own_dense_pointwise and own_dense_conv):
-        raise ValueError("own_dense_block needs own_dense_pointwise=True and own_dense_conv=True (the block buffer is read "
-                         "and written by their kernels)")
-    if own_dense_transition and key != 'densenet121':
-        raise ValueError("own_dense_transition is a switch of DenseNet-121 (no other network has transitions)")
-    if own_dense_transition and not own_dense_pointwise:
-        raise ValueError("own_dense_transition needs own_dense_pointwise=True (it switches the transitions that switch "
-                         "rewrites)")
-    if own_dense_stem and key != 'densenet121':
-        raise ValueError("own_dense_stem is a switch of DenseNet-121 (the ResNets have fuse_stem)")
-    if own_dense_stem and dtype != torch.bfloat16:
-        raise ValueError("own_dense_stem needs a bfloat16 network (the stem kernels produce bf16 activations)")
-    if own_dense_stem and not channels_last:
-        raise ValueError("own_dense_stem needs channels_last=True (the stem kernels produce channels_last storage)")
-    if own_dense_head not in (False, True, "inference"):
-        raise ValueError("own_dense_head must be False, True or 'inference'")
-    if own_dense_head and key != 'densenet121':
-        raise ValueError("own_dense_head is a switch of DenseNet-121 (MobileNetV2 and the ResNets have head_fp32)")
-    if own_dense_head and dtype != torch.bfloat16:
-        raise ValueError("own_dense_head needs a bfloat16 network (the head kernels work on bf16 activations)")
-    if own_dense_head and not channels_last:
-        raise ValueError("own_dense_head needs channels_last=True (the head kernels work on channels_last storage)")
-    if own_attention and key != 'vit_b_16':
-        raise ValueError("own_attention is a switch of ViT-B/16 (no other network has attention layers)")
-    if own_attention and dtype != torch.bfloat16:
-        raise ValueError("own_attention needs a bfloat16 network (the attention kernels work on bf16 activations)")
+    for row in SWITCHES:
+        _check_switch(row, values, key, dtype, channels_last)
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
         net = _BUILDERS[key](num_classes)
@@ -1681,30 +1704,10 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     net.eval()
     mean, std = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
     stem_fused = False
-    if own_depthwise:                    # after the weights are loaded: the tables are folded from them
-        use_own_depthwise_(net)
-    if own_pointwise:
-        use_own_pointwise_(net)
-    if own_first_conv:                   # the module normalises: the Sequential holds the network alone
-        use_own_first_conv_(net, mean, std)
-        stem_fused = True
-    if own_dense_pointwise:              # after the weights are loaded: the tables are derived from them
-        use_own_dense_pointwise_(net)
-    if own_dense_conv:                   # after the weights are loaded: the packed layouts are derived from them
-        use_own_dense_conv_(net)
-    if own_dense_block:                  # after the other two: it takes over the layers they have rewritten
-        use_own_dense_block_(net)
-    if own_dense_transition:             # after own_dense_pointwise: it switches the transitions that one creates
-        use_own_dense_transition_(net)
-    if own_dense_stem:                   # the module normalises: the Sequential holds the network alone
-        use_own_dense_stem_(net, mean, std)
-        stem_fused = True
-    if own_head:                         # after the weights are loaded: the head keeps an fp32 copy of the Linear
-        use_own_head_(net, head_fp32)
-    if own_dense_head:                   # after the weights are loaded: fp32 copies of the Linear and of norm5's affine map
-        use_own_dense_head_(net, own_dense_head)
-    if own_attention:
-        use_own_attention_(net)
+    for row in SWITCHES:                 # after the weights are loaded: tables and packed layouts are derived from them
+        if values[row.keyword]:
+            row.apply(net, *((mean, std) if row.normalises else ()), *((values[row.keyword],) if row.three_state else ()))
+            stem_fused = stem_fused or row.normalises
     if fuse_bn_act and isinstance(net, ResNet):
         stem_fused = bool(fuse_stem)
         if stem_fused and dtype != torch.bfloat16:
@@ -1723,3 +1726,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     if pad_input_channels and not stem_fused and not isinstance(net, VisionTransformer):   # ViT: patch embedding is a GEMM
         pad_first_conv_(net, pad_input_channels)
     return model
+
+
+build_classifier.__doc__ += "\n    The rows:\n" + "\n".join(
+    f"    {row.keyword} ({NETWORK_LABELS[row.network]}): {row.help}." for row in SWITCHES)

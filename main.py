@@ -12,6 +12,10 @@ from dl_attack_on_imagenet_amd import zoo
 DEFAULT_IMAGE = 'data/ImageNet/ILSVRC/Data/val/n01484850/ILSVRC2012_val_00002752.JPEG'   # main.py:69
 
 
+# the two-state DenseNet-121 rows; the head switches belong to the learner's CLI
+DENSE_ROWS = tuple(row for row in zoo.SWITCHES if row.network == 'densenet121' and not row.three_state)
+
+
 def load_image(path, size=224):
     """Resize(256) / CenterCrop(224) / ToTensor of the reference (main.py:64-75) without torchvision."""
     from PIL import Image
@@ -21,7 +25,8 @@ def load_image(path, size=224):
 
 
 def build_parser():
-    p = argparse.ArgumentParser()
+    p = argparse.ArgumentParser(description='Attack one image with a learned dictionary.  Any kernel switch that is on '
+                                            'makes the classifier a bfloat16 channels_last network (fp32 otherwise).')
     p.add_argument('--model', '-m', metavar='M', default='mobilenet')
     p.add_argument('--image', default=DEFAULT_IMAGE)
     p.add_argument('--weights', default=None)
@@ -30,25 +35,7 @@ def build_parser():
     p.add_argument('--figure', default='attack_samples.png')
     p.add_argument('--graph', type=int, default=1,
                    help='replay the inference iterations from a hipGraph (a one-image attack is launch-bound); 0 = eager')
-    p.add_argument('--own-dense-pointwise', type=int, default=0, choices=[0, 1],
-                   help='-m densenet: 1 = a bfloat16 channels_last network whose 61 pre-activated 1x1 layers run in the '
-                        'pre-activated pointwise kernels; 0 (default) = the fp32 library network.  Ignored otherwise')
-    p.add_argument('--own-dense-conv', type=int, default=0, choices=[0, 1],
-                   help='-m densenet: 1 = a bfloat16 channels_last network whose 58 3x3 growth convolutions run in the '
-                        '32-channel 3x3 kernels; 0 (default) = the library.  Independent of --own-dense-pointwise.  Ignored '
-                        'otherwise')
-    p.add_argument('--own-dense-block', type=int, default=0, choices=[0, 1],
-                   help='-m densenet: 1 = each of the 4 dense blocks runs on one channels_last feature buffer (no torch.cat, '
-                        'input gradients accumulated inside the 1x1 gradient kernel); needs --own-dense-pointwise 1 and '
-                        '--own-dense-conv 1; 0 (default) = per-layer tensors.  Ignored otherwise')
-    p.add_argument('--own-dense-transition', type=int, default=0, choices=[0, 1],
-                   help='-m densenet: 1 = each of the 3 transitions runs as one kernel that pools in front of the 1x1 '
-                        'convolution; needs --own-dense-pointwise 1; 0 (default) = the 1x1 kernel and the library pool.  '
-                        'Ignored otherwise')
-    p.add_argument('--own-dense-stem', type=int, default=0, choices=[0, 1],
-                   help='-m densenet: 1 = a bfloat16 channels_last network whose normalisation and conv0 / norm0 / relu0 / '
-                        'pool0 run in the stem kernels; 0 (default) = the library.  Independent of the other dense switches.  '
-                        'Ignored otherwise')
+    zoo.add_switch_arguments(p, DENSE_ROWS)
     return p
 
 
@@ -59,17 +46,11 @@ def main(args):
     torch.cuda.set_device(0)
     device = torch.device('cuda', 0)
     model_name = args.model.lower()          # names the dictionary file, as upstream (main.py:40, adil.py:89-91)
-    is_densenet = zoo.canonical_name(model_name) == 'densenet121'
-    own_dense_pw, own_dense_conv = bool(args.own_dense_pointwise) and is_densenet, bool(args.own_dense_conv) and is_densenet
-    own_dense_block = bool(args.own_dense_block) and is_densenet
-    own_dense_transition = bool(args.own_dense_transition) and is_densenet
-    own_dense_stem = bool(args.own_dense_stem) and is_densenet
-    own_dense = own_dense_pw or own_dense_conv or own_dense_block or own_dense_transition or own_dense_stem
+    switches, _ = zoo.switch_keywords(args, DENSE_ROWS, model_name, torch.bfloat16)
+    own_dense = any(switches.values())
     if own_dense:                            # the kernels work on bf16 channels_last activations
         net = zoo.build_classifier(model_name, weights=args.weights, device=device, dtype=torch.bfloat16,
-                                   channels_last=True, own_dense_pointwise=own_dense_pw, own_dense_conv=own_dense_conv,
-                                   own_dense_block=own_dense_block, own_dense_transition=own_dense_transition,
-                                   own_dense_stem=own_dense_stem)
+                                   channels_last=True, **switches)
         model = lambda x: net(x.to(torch.bfloat16)).float()
     else:
         net = model = zoo.build_classifier(model_name, weights=args.weights, device=device)
