@@ -11,6 +11,8 @@ Reference loops (file:line in flavie-yuan-liu/DL_attack_on_ImageNet):
 """
 from __future__ import annotations
 
+import contextlib
+import gc
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -42,6 +44,33 @@ def attack_loss(outputs: Tensor, labels: Tensor, loss: str, coeff: float, kappa:
     if loss == "logits":
         return margin_loss(outputs, labels, kappa).sum()
     raise ValueError(f"unknown loss {loss!r} (expected 'ce' or 'logits')")
+
+
+# --------------------------------------------------------------------------- #
+# hipGraph capture
+# --------------------------------------------------------------------------- #
+@contextlib.contextmanager
+def capture_graph(graph):
+    """`torch.cuda.graph(graph)` with Python's cyclic garbage collector run before the capture and held off during it.
+
+    A collection that happens to fall inside a capture runs the destructors of whatever dead cycle it finds there; if
+    that cycle holds GPU objects — an earlier solver or learner with its recorded graph, the graph's memory pool, the
+    pinned ring of its AdamW scalars and the ring's events (an exception's traceback is enough to close such a cycle) —
+    those destructors call into the HIP runtime while a global-mode capture is underway, which it does not allow: the
+    process aborted there, inside the collection, in the middle of DDragueSolver._capture (FINDINGS.md 45).  torch itself
+    no longer collects before a capture (torch.cuda.graph.__enter__ does so only with
+    torch.compiler.config.force_cudagraph_gc) and has never held the collector off during one.  So: collect first, where
+    the destructors are harmless, and let no collection start until the capture has ended; objects that die by reference
+    count are not affected.  The collector's state is put back as it was."""
+    gc.collect()
+    was_enabled = gc.isenabled()
+    gc.disable()
+    try:
+        with torch.cuda.graph(graph):
+            yield graph
+    finally:
+        if was_enabled:
+            gc.enable()
 
 
 # --------------------------------------------------------------------------- #
@@ -324,7 +353,7 @@ class DictionaryLearner:
             gl = labels.clone() if labels is not None else None
             t_d, t_v = self.sched_d.t, self.sched_v.t
             graph = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(graph):
+            with capture_graph(graph):
                 ls, fooled = self.step(model, gx, gi, gl)
             self.sched_d.t, self.sched_v.t = t_d, t_v            # capture records, it does not execute: no step was taken
             self._graph = (graph, gx, gi, ls, fooled, b, gl)
@@ -550,7 +579,7 @@ class DDragueSolver:
         t_sched, t_stop, iters = self.sched.t, self.stop.t, self.iters
         graph = torch.cuda.CUDAGraph()
         try:
-            with torch.cuda.graph(graph):
+            with capture_graph(graph):
                 for j in range(3):
                     self.iterate(dyn=self._dyn[j])
         finally:                                                 # recorded or failed: nothing was executed

@@ -11,6 +11,7 @@ import torch
 
 import attention_reference as aref
 from classifier_reference import BF16, CANARY, F32
+from graph_tools import assert_graph_used, no_capture_fallback
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -306,7 +307,9 @@ def test_attention_in_a_graphed_solver():
     x = torch.rand(8, 3, 32, 32, generator=g).to(DEV).to(BF16)
     d = (-1 + 2 * torch.rand(3, 32, 32, 6, generator=g)).to(DEV)
     eager = engine.DDragueSolver(net, x, d, 0.1, "logits").run(9)
-    graphed = engine.DDragueSolver(net, x, d, 0.1, "logits").run(9, use_graph=True)
+    with no_capture_fallback():                                     # a failed capture is an error, not an eager run
+        graphed = engine.DDragueSolver(net, x, d, 0.1, "logits").run(9, use_graph=True)
+    assert_graph_used(graphed)
     adv_e, adv_g = eager.result()[0], graphed.result()[0]
     assert graphed.iters == 9 and bool(torch.isfinite(adv_e.float()).all()) and bool((adv_e != x).any())
     assert _same_bits(adv_e, adv_g)

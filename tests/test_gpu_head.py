@@ -12,6 +12,7 @@ import torch.nn.functional as F
 
 import head_reference as href
 from classifier_reference import BF16, CANARY, F32
+from graph_tools import assert_graph_used, no_capture_fallback
 
 pytestmark = pytest.mark.gpu
 DEV = torch.device("cuda")
@@ -454,7 +455,9 @@ def test_inference_mode_enters_the_own_head_in_the_solver_only(monkeypatch):
     monkeypatch.undo()
     assert left == (0, 0, 0, 0), left                               # no library call is left in the classifier
     eager = engine.DDragueSolver(always, x, d, 0.1, "logits").run(9)
-    graphed = engine.DDragueSolver(always, x, d, 0.1, "logits").run(9, use_graph=True)
+    with no_capture_fallback():                                     # a failed capture is an error, not an eager run
+        graphed = engine.DDragueSolver(always, x, d, 0.1, "logits").run(9, use_graph=True)
+    assert_graph_used(graphed)
     adv_e, adv_g = eager.result()[0], graphed.result()[0]
     assert graphed.iters == 9 and bool(torch.isfinite(adv_e.float()).all()) and bool((adv_e != x).any())
     assert _same_bits(adv_e, adv_g)
