@@ -953,7 +953,116 @@ def conv3x3(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
     return Conv3x3Function.apply(x, wp_fwd, wp_bwd)
 
 
-CONV3X3_S2_MAX_W = 63        # ADIL_CONV3X3_S2_MAX_W of include/adil_hip.h
+def conv3x3_wide_covers(x: Tensor, cin: int, cout: int) -> bool:
+    """What adil_conv3x3_wide accepts: any width (anything else is ADIL_EINVAL and the caller keeps the library)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == cin and cin > 0 and cout > 0
+            and cin % 64 == 0 and cout % 64 == 0 and min(x.shape[0], x.shape[2], x.shape[3]) > 0
+            and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 and 9 * cin * cout < 2 ** 31)
+
+
+class Conv3x3WideFunction(torch.autograd.Function):
+    """`Conv3x3Function` on adil_conv3x3_wide: the same convolution, packs and bits on 2-D pixel tiles, for any width.
+    No weight gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, wp_fwd, wp_bwd):
+        lib = _lib.load()
+        b, c, h, w = x.shape
+        n = wp_fwd.shape[0]
+        x2 = _nhwc(x)
+        y = torch.empty((b, h, w, n), dtype=torch.bfloat16, device=x.device)
+        if b > 0:
+            _lib.check(lib.adil_conv3x3_wide(_ptr(x2), _ptr(wp_fwd), _ptr(y), b, h, w, c, n, _stream()), "adil_conv3x3_wide")
+        ctx.save_for_backward(wp_bwd)
+        ctx.meta = (c,)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        (wp_bwd,) = ctx.saved_tensors
+        (c,) = ctx.meta
+        g2 = _nhwc_grad(g)
+        b, h, w, n = g2.shape
+        gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
+        if b > 0:
+            _lib.check(lib.adil_conv3x3_wide(_ptr(g2), _ptr(wp_bwd), _ptr(gx), b, h, w, n, c, _stream()), "adil_conv3x3_wide")
+        return gx.permute(0, 3, 1, 2), None, None
+
+
+def conv3x3_wide(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
+    """x (B,C,H,W) bf16 in channels_last memory format -> its 3x3 / stride 1 / pad 1 convolution as (B,N,H,W), same
+    format, no copies, at any width.  wp_fwd (N, 9*C) and wp_bwd (C, 9*N) bf16 are the layouts of `pack_conv3x3_weights`."""
+    if wp_fwd.dim() != 2 or wp_bwd.dim() != 2 or wp_bwd.shape[0] == 0 or wp_fwd.shape[1] != 9 * wp_bwd.shape[0]:
+        raise ValueError(f"wp_fwd / wp_bwd must be the (N, 9C) / (C, 9N) matrices of pack_conv3x3_weights, got "
+                         f"{tuple(wp_fwd.shape)} / {tuple(wp_bwd.shape)}")
+    n, c = wp_fwd.shape[0], wp_bwd.shape[0]
+    if x.dim() == 4 and x.shape[0] == 0:                  # an empty batch is no kernel limit
+        if not (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == c):
+            raise ValueError(f"adil_conv3x3_wide does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
+    elif not conv3x3_wide_covers(x, c, n):
+        raise ValueError(f"adil_conv3x3_wide does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device} with a "
+                         f"{n} x {c} x 3 x 3 weight")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError("x must be in channels_last memory format (the kernel reads it in place)")
+    _check_operands(x.device, ("wp_fwd", wp_fwd, (n, 9 * c), torch.bfloat16), ("wp_bwd", wp_bwd, (c, 9 * n), torch.bfloat16))
+    return Conv3x3WideFunction.apply(x, wp_fwd, wp_bwd)
+
+
+def bias_relu_pool2_covers(x: Tensor) -> bool:
+    """What adil_bias_relu_pool2_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and min(x.shape) > 0 and x.shape[1] % 8 == 0
+            and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+
+
+class BiasReluPool2Function(torch.autograd.Function):
+    """max_pool2d(relu(x + bias[c]), 2) of a raw convolution output in one pass (adil_bias_relu_pool2_fwd), torch's fp32
+    chain bit for bit.  Only the winners' byte index is saved: the backward (adil_bias_relu_pool2_bwd) needs neither x
+    nor y.  No gradient for the bias: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, bias):
+        lib = _lib.load()
+        b, c, h, w = x.shape
+        x2 = _nhwc(x)
+        y = torch.empty((b, h // 2, w // 2, c), dtype=torch.bfloat16, device=x.device)
+        idx = torch.empty((b, h // 2, w // 2, c), dtype=torch.uint8, device=x.device)
+        if b > 0:
+            _lib.check(lib.adil_bias_relu_pool2_fwd(_ptr(x2), _ptr(bias), _ptr(y), _ptr(idx), b, h, w, c, _stream()),
+                       "adil_bias_relu_pool2_fwd")
+        ctx.save_for_backward(idx)
+        return y.permute(0, 3, 1, 2)
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        (idx,) = ctx.saved_tensors
+        g2 = _nhwc_grad(g)
+        b, oh, ow, c = g2.shape
+        gx = torch.empty((b, 2 * oh, 2 * ow, c), dtype=torch.bfloat16, device=g2.device)
+        if b > 0:
+            _lib.check(lib.adil_bias_relu_pool2_bwd(_ptr(g2), _ptr(idx), _ptr(gx), b, 2 * oh, 2 * ow, c, _stream()),
+                       "adil_bias_relu_pool2_bwd")
+        return gx.permute(0, 3, 1, 2), None
+
+
+def bias_relu_pool2(x: Tensor, bias: Optional[Tensor]) -> Tensor:
+    """x (B,C,H,W) bf16 in channels_last memory format, bias (C,) fp32 or None -> max_pool2d(relu(x + bias), 2) as
+    (B,C,H/2,W/2) bf16, same format, no copies."""
+    if x.dim() == 4 and x.shape[0] == 0:                  # an empty batch is no kernel limit
+        if not (x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] % 8 == 0 and x.shape[1] > 0
+                and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0):
+            raise ValueError(f"adil_bias_relu_pool2 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
+    elif not bias_relu_pool2_covers(x):
+        raise ValueError(f"adil_bias_relu_pool2 does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
+    if not x.permute(0, 2, 3, 1).is_contiguous():
+        raise ValueError("x must be in channels_last memory format (the kernel reads it in place)")
+    if bias is not None:
+        _check_operands(x.device, ("bias", bias, (x.shape[1],), torch.float32))
+    return BiasReluPool2Function.apply(x, bias)
+
+
+CONV3X3_S2_MAX_W = 63       # ADIL_CONV3X3_S2_MAX_W of include/adil_hip.h
 
 
 def pack_conv3x3_s2_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:

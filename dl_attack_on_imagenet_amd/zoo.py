@@ -1552,6 +1552,117 @@ def fit_centroid_head(model: nn.Module, images: torch.Tensor, labels: torch.Tens
     return top2[:, 0] - top2[:, 1], out.argmax(1)
 
 
+def _is_vgg_conv(conv) -> bool:
+    """A 3x3 / stride 1 / pad 1 Conv2d with a bias, dilation 1, one group, zero padding."""
+    return (isinstance(conv, nn.Conv2d) and conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1)
+            and conv.dilation == (1, 1) and conv.groups == 1 and conv.bias is not None and conv.padding_mode == 'zeros')
+
+
+def _is_pool2(m) -> bool:
+    return (isinstance(m, nn.MaxPool2d) and m.kernel_size in (2, (2, 2)) and m.stride in (2, (2, 2))
+            and m.padding in (0, (0, 0)) and m.dilation in (1, (1, 1)) and not m.ceil_mode and not m.return_indices)
+
+
+def _vgg_groups(features):
+    """The children of a VGG `features` as groups (conv, ReLU, MaxPool2d(2, 2) or None) of names, or None where they are
+    anything else.  The first convolution reads 3 channels."""
+    if not isinstance(features, nn.Sequential) or len(features) == 0:
+        return None
+    names, groups, i = list(features._modules), [], 0
+    while i < len(names):
+        if i + 1 >= len(names) or not _is_vgg_conv(features._modules[names[i]]) \
+                or not isinstance(features._modules[names[i + 1]], nn.ReLU):
+            return None
+        pooled = i + 2 < len(names) and _is_pool2(features._modules[names[i + 2]])
+        groups.append((names[i], names[i + 1], names[i + 2] if pooled else None))
+        i += 3 if pooled else 2
+    convs = [features._modules[g[0]] for g in groups]
+    chained = all(a.out_channels == b.in_channels for a, b in zip(convs, convs[1:]))
+    return groups if convs[0].in_channels == 3 and chained else None
+
+
+class _OwnVggFeatures(_KeepsFp32, nn.Sequential):
+    """`VGG11.features` with its groups conv, ReLU[, MaxPool2d(2, 2)] on the hand-written kernels where they cover the
+    input (CUDA, bf16, channels_last): a convolution with C % 64 == 0 and N % 64 == 0 runs in `ops.conv3x3` (W <= 63) or
+    `ops.conv3x3_wide` and leaves a raw output; a pooled group finishes in `ops.bias_relu_pool2(raw, bias)`, an unpooled
+    one in `ops.affine_act(raw, ones, bias)`.  The first convolution (3 channels) is called as the module it is, on a
+    CUDA bf16 input in any memory format, and its ReLU + pool run as `ops.bias_relu_pool2(out, None)` where its output is
+    channels_last.  Every other input (CPU, fp32, NCHW storage, an odd H or W in
+    front of a pool) keeps the original modules of that group, which stay the children under their names (same
+    state_dict keys).  Per covered convolution i the packs `wp_fwd_i` / `wp_bwd_i` (bf16) and the tables `bias_i` /
+    `ones_i` (kept fp32 through `.to(bfloat16)`) are non-persistent buffers derived from the weights held at rewrite time."""
+
+    def __init__(self, features: nn.Sequential):
+        groups = _vgg_groups(features)
+        if groups is None:
+            raise ValueError("not a VGG feature stack: groups of 3x3 / stride 1 / pad 1 convolution with bias, ReLU and an "
+                             "optional MaxPool2d(2, 2), the first convolution on 3 channels")
+        super().__init__(OrderedDict(features._modules))
+        self._groups, keep = groups, []
+        for conv_name, _, _ in groups:
+            conv = self._modules[conv_name]
+            if conv.in_channels % 64 or conv.out_channels % 64:
+                continue
+            wp_fwd, wp_bwd = ops.pack_conv3x3_weights(conv.weight)
+            self.register_buffer(f'wp_fwd_{conv_name}', wp_fwd, persistent=False)
+            self.register_buffer(f'wp_bwd_{conv_name}', wp_bwd, persistent=False)
+            self.register_buffer(f'bias_{conv_name}', conv.bias.detach().float().contiguous().clone(), persistent=False)
+            self.register_buffer(f'ones_{conv_name}', torch.ones(conv.out_channels, dtype=torch.float32,
+                                                                 device=conv.weight.device), persistent=False)
+            keep += [f'bias_{conv_name}', f'ones_{conv_name}']
+        self._KEEP_FP32 = tuple(keep)
+
+    def _own_group(self, x, conv_name, relu_name, pool_name):
+        """The group's output on the kernels, or None where they do not cover x."""
+        if not (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[0] > 0):
+            return None
+        pooled = pool_name is not None
+        if pooled and (x.shape[2] % 2 or x.shape[3] % 2):
+            return None
+        conv = self._modules[conv_name]
+        wp_fwd = self._buffers.get(f'wp_fwd_{conv_name}')
+        if wp_fwd is None:                                # the first convolution: the module as it is, then ReLU + pool
+            if not pooled:                                # on what the module returns (its 3-channel input is in any format)
+                return None
+            out = conv(x)
+            if ops.bias_relu_pool2_covers(out) and out.is_contiguous(memory_format=torch.channels_last):
+                return ops.bias_relu_pool2(out, None)
+            return self._modules[pool_name](self._modules[relu_name](out))
+        if not x.is_contiguous(memory_format=torch.channels_last):
+            return None
+        wp_bwd, bias = self._buffers[f'wp_bwd_{conv_name}'], self._buffers[f'bias_{conv_name}']
+        c, n = wp_bwd.shape[0], wp_fwd.shape[0]
+        if not (ops.conv3x3_wide_covers(x, c, n) and wp_fwd.dtype == torch.bfloat16 and wp_fwd.device == x.device
+                and wp_bwd.device == x.device and bias.device == x.device):
+            return None
+        raw = ops.conv3x3(x, wp_fwd, wp_bwd) if x.shape[3] <= 63 else ops.conv3x3_wide(x, wp_fwd, wp_bwd)
+        if pooled:
+            return ops.bias_relu_pool2(raw, bias)
+        return ops.affine_act(raw, self._buffers[f'ones_{conv_name}'], bias, relu=True)
+
+    def forward(self, x):
+        for conv_name, relu_name, pool_name in self._groups:
+            y = self._own_group(x, conv_name, relu_name, pool_name)
+            if y is None:
+                y = self._modules[relu_name](self._modules[conv_name](x))
+                if pool_name is not None:
+                    y = self._modules[pool_name](y)
+            x = y
+        return x
+
+
+def use_own_vgg_conv_(net: nn.Module) -> int:
+    """Replace `features` of a VGG by an `_OwnVggFeatures`; returns the number of convolutions that got packs (VGG11: 7).
+    A network without that structure is a ValueError."""
+    features = net._modules.get('features')
+    if _vgg_groups(features) is None:
+        raise ValueError("own_vgg_conv needs a VGG: a `features` stack of 3x3 convolution + ReLU groups with optional "
+                         "MaxPool2d(2, 2)")
+    own = _OwnVggFeatures(features)
+    net._modules['features'] = own
+    return sum(1 for name in own._buffers if name.startswith('wp_fwd_'))
+
+
 # ----------------------------------------------------------------------------- the kernel switches
 class Switch(NamedTuple):
     """One kernel switch of `build_classifier`: a keyword there and a flag of the CLIs."""
@@ -1572,7 +1683,7 @@ class Switch(NamedTuple):
         return self.flag.lstrip('-').replace('-', '_')
 
 
-NETWORK_LABELS = {'mobilenet_v2': 'MobileNetV2', 'densenet121': 'DenseNet-121', 'vit_b_16': 'ViT-B/16'}
+NETWORK_LABELS = {'mobilenet_v2': 'MobileNetV2', 'densenet121': 'DenseNet-121', 'vit_b_16': 'ViT-B/16', 'vgg11': 'VGG11'}
 
 # In the order they are applied (a row that `requires` others comes behind them).  A new switch is one row here and its
 # use_own_*_ function; build_classifier's keyword of the same name is the only other line.
@@ -1612,6 +1723,15 @@ SWITCHES = (
            channels_last=False),
 )
 _SWITCH = {row.keyword: row for row in SWITCHES}
+
+# A second table, checked and applied after the first with the same code: `SWITCHES` is compared row for row with a
+# recorded grid (tests/golden/classifier_switch_grid.json), so rows of networks added later live here.
+VGG_SWITCHES = (
+    Switch('own_vgg_conv', '--own-vgg-conv', 'vgg11', '3x3', use_own_vgg_conv_,
+           'the 3x3 convolutions with 64-channel granularity (7 of 8) run in the 3x3 kernels, the wide-image one where '
+           'W > 63; bias + ReLU + 2x2 max-pool run in one pass each way, the first convolution stays on the library '
+           '(`_OwnVggFeatures`)'),
+)
 
 
 def _check_switch(row: Switch, values: dict, key: str, dtype, channels_last: bool) -> None:
@@ -1669,7 +1789,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      own_first_conv: bool = False, own_dense_pointwise: bool = False,
                      own_dense_conv: bool = False, own_dense_block: bool = False,
                      own_dense_transition: bool = False, own_dense_stem: bool = False,
-                     own_dense_head=False, own_attention: bool = False) -> nn.Module:
+                     own_dense_head=False, own_attention: bool = False, own_vgg_conv: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen: the object both CLIs hand to ADIL.  Everything below is
     a function-preserving rewrite, off by default, applied after the weights are loaded.
     fold_bn folds every BatchNorm into its convolution; pad_input_channels zero-pads the first convolution's input.
@@ -1677,7 +1797,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     constructor's: fuse_stem (bf16 only) moves the normalisation and the first stage into the stem kernels, head_fp32
     keeps global pooling + the last linear layer in fp32 (True = always, "inference" = only inside engine.precise_head),
     own_strided_conv runs the stride-2 3x3 convolutions in the hand-written kernel; see `FusedResNet`.
-    Every other keyword is a row of `SWITCHES`, which says what it needs (its network, bf16, channels_last, other
+    Every other keyword is a row of `SWITCHES` or `VGG_SWITCHES`, which says what it needs (its network, bf16, channels_last, other
     switches) and what it does; on MobileNetV2 head_fp32 is such a row.  A switch that is on where it cannot work is a
     ValueError, never a silent fall-back.  Where a stem is fused (fuse_stem or a row that normalises) the Sequential
     holds the network alone."""
@@ -1685,7 +1805,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
-    values = {row.keyword: given[row.keyword] for row in SWITCHES}
+    values = {row.keyword: given[row.keyword] for row in SWITCHES + VGG_SWITCHES}
     if key != _SWITCH['head_fp32'].network:              # elsewhere head_fp32 is FusedResNet's argument, not the row
         values['head_fp32'] = False
     if head_fp32 and not fuse_bn_act and not values['head_fp32']:
@@ -1693,7 +1813,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     _check_switch(_SWITCH['head_fp32'], values, key, dtype, channels_last)    # with the other head_fp32 checks, as ever
     if own_strided_conv and not fuse_bn_act:
         raise ValueError("own_strided_conv is a switch of the FusedResNet path (fuse_bn_act=True)")
-    for row in SWITCHES:
+    for row in SWITCHES + VGG_SWITCHES:
         _check_switch(row, values, key, dtype, channels_last)
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
@@ -1704,7 +1824,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     net.eval()
     mean, std = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
     stem_fused = False
-    for row in SWITCHES:                 # after the weights are loaded: tables and packed layouts are derived from them
+    for row in SWITCHES + VGG_SWITCHES:  # after the weights are loaded: tables and packed layouts are derived from them
         if values[row.keyword]:
             row.apply(net, *((mean, std) if row.normalises else ()), *((values[row.keyword],) if row.three_state else ()))
             stem_fused = stem_fused or row.normalises
@@ -1729,4 +1849,4 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
 
 
 build_classifier.__doc__ += "\n    The rows:\n" + "\n".join(
-    f"    {row.keyword} ({NETWORK_LABELS[row.network]}): {row.help}." for row in SWITCHES)
+    f"    {row.keyword} ({NETWORK_LABELS[row.network]}): {row.help}." for row in SWITCHES + VGG_SWITCHES)

@@ -57,7 +57,8 @@ extern "C" {
  * adil_dense3x3_fwd_ld / adil_dense3x3_bwd_ld after those, and adil_dense_transition_fwd / _bwd after those, and adil_bn_pool_head_fwd / adil_bn_pool_head_bwd after those, and
  * adil_attn_max_tokens / adil_attn_fwd / adil_attn_bwd after those: all additive
  * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls
- * neither), and adil_pw_conv_fwd_tile after them.  adil_conv3x3_loop / adil_stem_bwd_variant were two more of that kind, added under 8 and removed again under 8
+ * neither), and adil_pw_conv_fwd_tile after them, and adil_conv3x3_wide / adil_bias_relu_pool2_fwd / _bwd after
+ * those.  adil_conv3x3_loop / adil_stem_bwd_variant were two more of that kind, added under 8 and removed again under 8
  * with the kernels they selected: library and binding are built from one tree. */
 int adil_abi_version(void);
 
@@ -684,6 +685,32 @@ int adil_attn_max_tokens(void);
 int adil_attn_fwd(const void* qkv, void* o, float* lse, int B, int T, int H, void* stream);
 int adil_attn_bwd(const void* qkv, const void* o, const float* lse, const void* go, void* gqkv, int B, int T, int H,
                   void* stream);
+
+/* adil_conv3x3 for ANY width (the 3x3 convolutions of a frozen VGG; added under ABI 8 like the entry points above):
+ * exactly its contract — channels_last bf16 x[B][H][W][C], weights wp[N][9][C] of the same two packs, raw bf16
+ * y[B][H][W][N], the input gradient the same call on the flipped pack with C and N exchanged, bf16 MFMA products with
+ * fp32 accumulation and one RNE rounding (a zero sum is written as +0) — on 2-D pixel tiles inside one image (8 x 16
+ * pixels x 128 channels where N % 128 == 0, else 16 x 16 x 64) instead of linear ones.  A halo pixel outside the image is
+ * staged as zeros by selection; its load goes to the nearest pixel of the same image, so nothing of a neighbouring image or
+ * outside the operand is read and a NaN or Inf next door never meets a multiplier.  Per accumulator the MFMAs run in
+ * adil_conv3x3's order (chunk -> tap -> k), so both give the same bits where both accept the shape.
+ * Limits: C % 64 == 0, N % 64 == 0, B, H, W >= 1 (any W), B * H * W < 2^31, 9 * C * N < 2^31, non-null 16-byte aligned
+ * pointers; anything else ADIL_EINVAL before any launch, outputs untouched.  One launch on `stream`, no allocation, no
+ * atomics (bitwise reproducible), capturable, 64-bit element offsets; every element of y is written, nothing behind it. */
+int adil_conv3x3_wide(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream);
+
+/* bias + ReLU + 2x2 / stride 2 max-pool behind a raw convolution output, and its input gradient (added under ABI 8):
+ *     x, gx [B][H][W][C] bf16      bias [C] fp32 or NULL      y, g [B][H/2][W/2][C] bf16      idx [B][H/2][W/2][C] uint8
+ * Forward, per window and channel: t = fp32(x) + bias[c] (one fp32 add); the winner is the first of (0,0), (0,1), (1,0),
+ * (1,1) that is strictly greater than all before it; y = bf16_rne(max(t_winner, 0)) with a zero written as +0;
+ * idx = dh * 2 + dw of the winner, or 4 where t_winner <= 0 (a dead window).  Backward: gx at the winner's position takes
+ * the bits of g, every other element — all four of a dead window — is +0, and every element of gx is written.  That is
+ * torch's fp32 chain max_pool2d(relu(x.float() + bias), 2) and its autograd bit for bit, ties included.
+ * Limits: H, W even, C % 8 == 0, B, H, W, C >= 1, B * H * W < 2^31, non-null pointers aligned to 16 bytes (idx: 8);
+ * anything else ADIL_EINVAL before any launch, outputs untouched.  One launch each, no allocation, no atomics,
+ * capturable, 64-bit element offsets. */
+int adil_bias_relu_pool2_fwd(const void* x, const float* bias, void* y, void* idx, int B, int H, int W, int C, void* stream);
+int adil_bias_relu_pool2_bwd(const void* g, const void* idx, void* gx, int B, int H, int W, int C, void* stream);
 
 #ifdef __cplusplus
 }
