@@ -69,6 +69,7 @@ def build_parser():
         'kernel switches', 'Each belongs to one network and needs --dtype bf16; it is ignored otherwise.  A switch that '
                            'needs channels_last storage makes the network channels_last.'))
     zoo.add_switch_arguments(p, zoo.VGG_SWITCHES)
+    zoo.add_switch_arguments(p, zoo.VGG_FIRST_SWITCHES)
     return p
 
 
@@ -169,12 +170,15 @@ def main(args):
 def classifier_keywords(args, model_name, dtype):
     """What the flags ask of zoo.build_classifier: --fast-classifier (bf16 ResNets: the FusedResNet path with the fused
     stem and fp32 logits inside the DDrague inference loop) and the rows of zoo.SWITCHES; on VGG11 those of
-    zoo.VGG_SWITCHES as well."""
+    zoo.VGG_SWITCHES as well, and those of zoo.VGG_FIRST_SWITCHES where their flag is on."""
     fast = bool(args.fast_classifier) and dtype == torch.bfloat16 and zoo.canonical_name(model_name).startswith('resnet')
     kw, needs_channels_last = zoo.switch_keywords(args, zoo.SWITCHES, model_name, dtype)
     if zoo.canonical_name(model_name) == 'vgg11':
         vgg, vgg_channels_last = zoo.switch_keywords(args, zoo.VGG_SWITCHES, model_name, dtype)
         kw, needs_channels_last = dict(kw, **vgg), needs_channels_last or vgg_channels_last
+        first, first_channels_last = zoo.switch_keywords(args, zoo.VGG_FIRST_SWITCHES, model_name, dtype)
+        if any(first.values()):                              # only when on: with the flag off the dictionary is as it was
+            kw, needs_channels_last = dict(kw, **first), needs_channels_last or first_channels_last
     if fast:
         kw['head_fp32'] = "inference"
     return dict(kw, channels_last=fast or needs_channels_last, fuse_bn_act=fast, fuse_stem=fast,

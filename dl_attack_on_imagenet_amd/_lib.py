@@ -116,6 +116,10 @@ SIGNATURES = {
     "adil_conv3x3_wide": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
     "adil_bias_relu_pool2_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
     "adil_bias_relu_pool2_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p]),
+    "adil_first3x3_pool_fwd": (c_int, [c_void_p, c_int, c_void_p, c_float, c_float, c_float, c_float, c_float, c_float,
+                                       c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
+    "adil_first3x3_pool_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_float, c_float, c_float, c_void_p, c_int, c_int,
+                                       c_int, c_int, c_void_p]),
 }
 
 ABI_VERSION = 8

@@ -1716,6 +1716,72 @@ def first_conv3x3(x: Tensor, w_fwd: Tensor, w_bwd: Tensor, scale: Tensor, shift:
     return FirstConv3x3Function.apply(x, w_fwd, w_bwd, scale, shift, mean, inv_std, bool(relu6))
 
 
+def pack_first3x3_pool_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
+    """(64,3,3,3) conv weight -> the two bf16 layouts of adil_first3x3_pool_fwd / _bwd (include/adil_hip.h), both 2-D for
+    the reason `pack_first3x3_weights` gives: w_fwd [64][3*4*4] (w[n][c][kh][kw] at [n][kh][kw][c], zero for kw = 3 /
+    c = 3) and w_bwd [3][9*64] (w[n][c][kh][kw] at [c][kh*3+kw][n]: channels swapped, taps NOT flipped)."""
+    if tuple(weight.shape) != (64, 3, 3, 3):
+        raise ValueError(f"the VGG first-convolution kernels are written for a (64,3,3,3) convolution, got {tuple(weight.shape)}")
+    w = weight.detach().float()
+    wf = torch.zeros(64, 3, 4, 4, dtype=torch.float32, device=w.device)
+    wf[:, :, :3, :3] = w.permute(0, 2, 3, 1)                       # [n][kh][kw][c]
+    wb = w.permute(1, 2, 3, 0).reshape(3, 9 * 64)                   # [c][kh*3+kw][n]
+    return wf.to(torch.bfloat16).reshape(64, 48).contiguous(), wb.to(torch.bfloat16).contiguous()
+
+
+def first_conv3x3_pool_covers(x: Tensor) -> bool:
+    """What adil_first3x3_pool_fwd / _bwd accept (anything else is ADIL_EINVAL and the caller keeps the library)."""
+    return (x.dim() == 4 and x.is_cuda and x.dtype in _DTYPE_CODE and x.shape[1] == 3 and x.shape[2] >= 2
+            and x.shape[3] >= 2 and x.shape[2] % 2 == 0 and x.shape[3] % 2 == 0 and 0 < x.shape[0] <= FIRST3X3_MAX_BATCH
+            and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31)
+
+
+class FirstConv3x3PoolFunction(torch.autograd.Function):
+    """Normalize -> conv3x3 (3 -> 64, bias) -> ReLU -> MaxPool2d(2, 2) of a frozen VGG11 as one HIP kernel
+    (adil_first3x3_pool_fwd) and its input gradient as another (adil_first3x3_pool_bwd).  Only the winners' byte index is
+    saved: the backward needs neither x nor y.  x: (B,3,H,W) fp32/bf16 contiguous NCHW; returns (B,64,H/2,W/2) bf16 in
+    channels_last storage.  The gradient comes back in x's dtype and layout.  No weight gradient: the network is frozen."""
+
+    @staticmethod
+    def forward(ctx, x, w_fwd, w_bwd, bias, mean, inv_std):
+        lib = _lib.load()
+        b, _, h, w = x.shape
+        y = torch.empty((b, h // 2, w // 2, 64), dtype=torch.bfloat16, device=x.device)
+        idx = torch.empty((b, h // 2, w // 2, 64), dtype=torch.uint8, device=x.device)
+        _lib.check(lib.adil_first3x3_pool_fwd(_ptr(x), stream_dtype_code(x.dtype), _ptr(w_fwd), *mean, *inv_std, _ptr(bias),
+                                              _ptr(y), _ptr(idx), b, h, w, _stream()), "adil_first3x3_pool_fwd")
+        ctx.save_for_backward(w_bwd, idx)
+        ctx.meta = (h, w, x.dtype, inv_std)
+        return y.permute(0, 3, 1, 2)                                 # logical NCHW, channels_last storage
+
+    @staticmethod
+    def backward(ctx, g):
+        lib = _lib.load()
+        w_bwd, idx = ctx.saved_tensors
+        h, w, xdtype, inv_std = ctx.meta
+        g2 = _nhwc_grad(g)
+        b = g2.shape[0]
+        gx = torch.empty((b, 3, h, w), dtype=xdtype, device=g2.device)
+        _lib.check(lib.adil_first3x3_pool_bwd(_ptr(g2), _ptr(idx), _ptr(w_bwd), *inv_std, _ptr(gx), stream_dtype_code(xdtype),
+                                              b, h, w, _stream()), "adil_first3x3_pool_bwd")
+        return (gx,) + (None,) * 5
+
+
+def first_conv3x3_pool(x: Tensor, w_fwd: Tensor, w_bwd: Tensor, bias: Tensor, mean, inv_std) -> Tensor:
+    """x (B,3,H,W) fp32 / bf16, contiguous NCHW, H and W even -> max_pool2d(relu(conv3x3((x - mean) / std) + bias), 2) as
+    (B,64,H/2,W/2) bf16 in channels_last memory format, no copies.  mean / inv_std: three floats each."""
+    if not first_conv3x3_pool_covers(x):
+        raise ValueError(f"adil_first3x3_pool does not cover a {tuple(x.shape)} {x.dtype} tensor on {x.device}")
+    if not x.is_contiguous():
+        raise ValueError("x must be contiguous (NCHW)")
+    _check_operands(x.device, ("w_fwd", w_fwd, (64, 48), torch.bfloat16), ("w_bwd", w_bwd, (3, 576), torch.bfloat16),
+                    ("bias", bias, (64,), torch.float32))
+    mean, inv_std = tuple(float(m) for m in mean), tuple(float(s) for s in inv_std)
+    if len(mean) != 3 or len(inv_std) != 3:
+        raise ValueError("mean and inv_std must hold three values each")
+    return FirstConv3x3PoolFunction.apply(x, w_fwd, w_bwd, bias, mean, inv_std)
+
+
 # --------------------------------------------------------------------------- #
 POOL_HEAD_CHANNELS = range(8, 2048 + 1, 8)   # channel counts of adil_pool_head_fwd / _bwd (include/adil_hip.h)
 POOL_HEAD_MAX_PIXELS = 65536

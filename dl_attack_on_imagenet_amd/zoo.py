@@ -1640,14 +1640,61 @@ class _OwnVggFeatures(_KeepsFp32, nn.Sequential):
             return ops.bias_relu_pool2(raw, bias)
         return ops.affine_act(raw, self._buffers[f'ones_{conv_name}'], bias, relu=True)
 
+    def take_first_group_(self, mean, std) -> None:
+        """Take over the `Normalize` in front of the network and run it with the first group (conv 3 -> 64, ReLU,
+        MaxPool2d(2, 2)) as one kernel each way (`ops.first_conv3x3_pool`) where that covers the input: CUDA, fp32 or bf16
+        (B,3,H,W) with even H and W, a bf16 network.  On every other input `forward` normalises exactly as
+        `Normalize.forward` does and the group runs as before.  Non-persistent buffers of their own: the packs
+        `first_w_fwd` / `first_w_bwd` (bf16), `first_bias` (kept fp32) and the tables `norm_mean` / `norm_std`."""
+        conv_name, _, pool_name = self._groups[0]
+        conv = self._modules[conv_name]
+        if pool_name is None or conv.out_channels != 64:
+            raise ValueError("the first group must be conv 3 -> 64, ReLU, MaxPool2d(2, 2)")
+        w_fwd, w_bwd = ops.pack_first3x3_pool_weights(conv.weight)
+        dev = conv.weight.device
+        for name, t in (('first_w_fwd', w_fwd), ('first_w_bwd', w_bwd),
+                        ('first_bias', conv.bias.detach().float().contiguous().clone()),
+                        ('norm_mean', torch.tensor([float(v) for v in mean], dtype=torch.float32, device=dev)),
+                        ('norm_std', torch.tensor([float(v) for v in std], dtype=torch.float32, device=dev))):
+            self.register_buffer(name, t, persistent=False)
+        self._KEEP_FP32 = tuple(self._KEEP_FP32) + ('first_bias',)
+        self.mean = [float(m) for m in mean]
+        self.inv_std = [1.0 / float(s) for s in std]
+
+    def _own_first_group(self, x):
+        """The first group's output from the raw input on the fused kernels, or None where they do not cover x."""
+        w_fwd = self._buffers['first_w_fwd']
+        if not (ops.first_conv3x3_pool_covers(x) and self._modules[self._groups[0][0]].weight.dtype == torch.bfloat16
+                and w_fwd.dtype == torch.bfloat16 and w_fwd.device == x.device and self.first_bias.device == x.device):
+            return None
+        return ops.first_conv3x3_pool(x.contiguous(), w_fwd, self._buffers['first_w_bwd'], self.first_bias, self.mean,
+                                      self.inv_std)
+
+    def _group(self, x, conv_name, relu_name, pool_name):
+        """One group on the kernels where they cover x, else on its original modules."""
+        y = self._own_group(x, conv_name, relu_name, pool_name)
+        if y is None:
+            y = self._modules[relu_name](self._modules[conv_name](x))
+            if pool_name is not None:
+                y = self._modules[pool_name](y)
+        return y
+
+    def first_group(self, x):
+        """The first group's output as `forward` computes it; x is the raw input once `take_first_group_` has made the
+        normalisation this module's, the normalised one before (tools/bench_vgg_first_conv.py times both)."""
+        if 'first_w_fwd' in self._buffers:
+            y = self._own_first_group(x)
+            if y is not None:
+                return y
+            mean = self.norm_mean.reshape(1, -1, 1, 1).to(x.dtype)      # `Normalize.forward`, operation for operation
+            std = self.norm_std.reshape(1, -1, 1, 1).to(x.dtype)
+            x = (x - mean) / std
+        return self._group(x, *self._groups[0])
+
     def forward(self, x):
-        for conv_name, relu_name, pool_name in self._groups:
-            y = self._own_group(x, conv_name, relu_name, pool_name)
-            if y is None:
-                y = self._modules[relu_name](self._modules[conv_name](x))
-                if pool_name is not None:
-                    y = self._modules[pool_name](y)
-            x = y
+        x = self.first_group(x)
+        for group in self._groups[1:]:
+            x = self._group(x, *group)
         return x
 
 
@@ -1661,6 +1708,17 @@ def use_own_vgg_conv_(net: nn.Module) -> int:
     own = _OwnVggFeatures(features)
     net._modules['features'] = own
     return sum(1 for name in own._buffers if name.startswith('wp_fwd_'))
+
+
+def use_own_vgg_first_conv_(net: nn.Module, mean, std) -> int:
+    """Hand the normalisation and the first group of a VGG that `use_own_vgg_conv_` has rewritten to the fused
+    first-convolution kernels (`_OwnVggFeatures.take_first_group_`): the caller must no longer put a `Normalize` in front
+    of the network.  Returns how many groups were taken (1)."""
+    features = net._modules.get('features')
+    if not isinstance(features, _OwnVggFeatures):
+        raise ValueError("own_vgg_first_conv works on the `_OwnVggFeatures` that own_vgg_conv puts in place of `features`")
+    features.take_first_group_(mean, std)
+    return 1
 
 
 # ----------------------------------------------------------------------------- the kernel switches
@@ -1733,6 +1791,16 @@ VGG_SWITCHES = (
            '(`_OwnVggFeatures`)'),
 )
 
+# A third table for the same reason: `VGG_SWITCHES` is pinned as the one row it was merged with.
+VGG_FIRST_SWITCHES = (
+    Switch('own_vgg_first_conv', '--own-vgg-first-conv', 'vgg11', 'first-convolution', use_own_vgg_first_conv_,
+           'the normalisation and the first group (conv 3 -> 64, ReLU, 2x2 max-pool) run as one kernel each way on the '
+           'attack\'s own tensors, so the trunk calls no library convolution, ReLU or pooling '
+           '(`_OwnVggFeatures.take_first_group_`)', requires=('own_vgg_conv',), normalises=True),
+)
+ALL_SWITCHES = SWITCHES + VGG_SWITCHES + VGG_FIRST_SWITCHES
+_ANY_SWITCH = {row.keyword: row for row in ALL_SWITCHES}
+
 
 def _check_switch(row: Switch, values: dict, key: str, dtype, channels_last: bool) -> None:
     """One row's conditions, in the order value, network, required switches, bf16, channels_last."""
@@ -1757,7 +1825,7 @@ def add_switch_arguments(parser, rows=SWITCHES) -> None:
     for row in rows:
         text = f"{NETWORK_LABELS[row.network]}: {row.help}"
         if row.requires:
-            text += "; needs " + " and ".join(f"{_SWITCH[r].flag} 1" for r in row.requires)
+            text += "; needs " + " and ".join(f"{_ANY_SWITCH[r].flag} 1" for r in row.requires)
         if row.three_state:
             text += "; inference = only inside the DDrague inference loop (engine.precise_head), always = in every call"
             parser.add_argument(row.flag, default='0', choices=['0', 'inference', 'always'],
@@ -1789,7 +1857,8 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
                      own_first_conv: bool = False, own_dense_pointwise: bool = False,
                      own_dense_conv: bool = False, own_dense_block: bool = False,
                      own_dense_transition: bool = False, own_dense_stem: bool = False,
-                     own_dense_head=False, own_attention: bool = False, own_vgg_conv: bool = False) -> nn.Module:
+                     own_dense_head=False, own_attention: bool = False, own_vgg_conv: bool = False,
+                     own_vgg_first_conv: bool = False) -> nn.Module:
     """Sequential(Normalize, net), eval mode, parameters frozen: the object both CLIs hand to ADIL.  Everything below is
     a function-preserving rewrite, off by default, applied after the weights are loaded.
     fold_bn folds every BatchNorm into its convolution; pad_input_channels zero-pads the first convolution's input.
@@ -1797,7 +1866,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     constructor's: fuse_stem (bf16 only) moves the normalisation and the first stage into the stem kernels, head_fp32
     keeps global pooling + the last linear layer in fp32 (True = always, "inference" = only inside engine.precise_head),
     own_strided_conv runs the stride-2 3x3 convolutions in the hand-written kernel; see `FusedResNet`.
-    Every other keyword is a row of `SWITCHES` or `VGG_SWITCHES`, which says what it needs (its network, bf16, channels_last, other
+    Every other keyword is a row of `SWITCHES`, `VGG_SWITCHES` or `VGG_FIRST_SWITCHES`, which says what it needs (its network, bf16, channels_last, other
     switches) and what it does; on MobileNetV2 head_fp32 is such a row.  A switch that is on where it cannot work is a
     ValueError, never a silent fall-back.  Where a stem is fused (fuse_stem or a row that normalises) the Sequential
     holds the network alone."""
@@ -1805,7 +1874,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     key = canonical_name(name)
     if head_fp32 not in (False, True, "inference"):
         raise ValueError("head_fp32 must be False, True or 'inference'")
-    values = {row.keyword: given[row.keyword] for row in SWITCHES + VGG_SWITCHES}
+    values = {row.keyword: given[row.keyword] for row in ALL_SWITCHES}
     if key != _SWITCH['head_fp32'].network:              # elsewhere head_fp32 is FusedResNet's argument, not the row
         values['head_fp32'] = False
     if head_fp32 and not fuse_bn_act and not values['head_fp32']:
@@ -1813,7 +1882,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     _check_switch(_SWITCH['head_fp32'], values, key, dtype, channels_last)    # with the other head_fp32 checks, as ever
     if own_strided_conv and not fuse_bn_act:
         raise ValueError("own_strided_conv is a switch of the FusedResNet path (fuse_bn_act=True)")
-    for row in SWITCHES + VGG_SWITCHES:
+    for row in ALL_SWITCHES:
         _check_switch(row, values, key, dtype, channels_last)
     with torch.random.fork_rng(devices=[]):
         torch.manual_seed(seed)
@@ -1824,7 +1893,7 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
     net.eval()
     mean, std = [0.485, 0.456, 0.406], [0.229, 0.224, 0.225]
     stem_fused = False
-    for row in SWITCHES + VGG_SWITCHES:  # after the weights are loaded: tables and packed layouts are derived from them
+    for row in ALL_SWITCHES:  # after the weights are loaded: tables and packed layouts are derived from them
         if values[row.keyword]:
             row.apply(net, *((mean, std) if row.normalises else ()), *((values[row.keyword],) if row.three_state else ()))
             stem_fused = stem_fused or row.normalises
@@ -1849,4 +1918,4 @@ def build_classifier(name: str, num_classes: int = 1000, seed: int = 0, weights:
 
 
 build_classifier.__doc__ += "\n    The rows:\n" + "\n".join(
-    f"    {row.keyword} ({NETWORK_LABELS[row.network]}): {row.help}." for row in SWITCHES + VGG_SWITCHES)
+    f"    {row.keyword} ({NETWORK_LABELS[row.network]}): {row.help}." for row in ALL_SWITCHES)

@@ -58,7 +58,7 @@ extern "C" {
  * adil_attn_max_tokens / adil_attn_fwd / adil_attn_bwd after those: all additive
  * under 8, and so are adil_pw_conv_bwd_tile / adil_pw_route_policy (test and tool entry points: the product calls
  * neither), and adil_pw_conv_fwd_tile after them, and adil_conv3x3_wide / adil_bias_relu_pool2_fwd / _bwd after
- * those.  adil_conv3x3_loop / adil_stem_bwd_variant were two more of that kind, added under 8 and removed again under 8
+ * those, and adil_first3x3_pool_fwd / adil_first3x3_pool_bwd after those.  adil_conv3x3_loop / adil_stem_bwd_variant were two more of that kind, added under 8 and removed again under 8
  * with the kernels they selected: library and binding are built from one tree. */
 int adil_abi_version(void);
 
@@ -711,6 +711,39 @@ int adil_conv3x3_wide(const void* x, const void* wp, void* y, int B, int H, int 
  * capturable, 64-bit element offsets. */
 int adil_bias_relu_pool2_fwd(const void* x, const float* bias, void* y, void* idx, int B, int H, int W, int C, void* stream);
 int adil_bias_relu_pool2_bwd(const void* g, const void* idx, void* gx, int B, int H, int W, int C, void* stream);
+
+/* The first group of a frozen VGG11 — Normalize, conv 3 -> 64 (3x3, stride 1, pad 1, bias), ReLU, MaxPool2d(2, 2) — as one
+ * kernel each way on the attack's own tensors (added under ABI 8).  The 64-channel tensor at H x W never reaches memory.
+ *     x, gx [B][3][H][W] NCHW, fp32 or bf16 (x_dtype / gx_dtype: ADIL_F32 / ADIL_BF16), as in adil_first3x3_fwd / _bwd
+ *     y, g  [B][H/2][W/2][64] bf16 channels_last      idx [B][H/2][W/2][64] uint8, the format of adil_bias_relu_pool2_*
+ *     w_fwd [64][3][4][4] bf16 = w[n][c][kh][kw] at [n][kh][kw][c], zero for kw = 3 / c = 3
+ *     w_bwd [3][9][64] bf16 = w[n][c][kh][kw] at [c][kh*3+kw][n] (channels swapped, taps NOT flipped)      bias [64] fp32
+ * Forward:
+ *     x' = bf16( f32( f32(x - mean[c]) * inv_std[c] ) ): the subtraction and the product each rounded to fp32 on its own
+ *          (no contraction), then one RNE rounding; the zero padding is applied to x', the NORMALISED tensor.
+ *     s  = sum over the 27 taps of x' * w: bf16 MFMA products (exact in fp32), fp32 accumulation, one instruction per tap
+ *          row kh with the K order (kw, c).
+ *     t  = s + bias[n]: one fp32 add, no bf16 rounding in between.
+ *     The winner of a 2x2 window is the first of (0,0), (0,1), (1,0), (1,1) that is strictly greater than all before it,
+ *     compared on the fp32 t; y = bf16_rne(max(t_winner, 0)) with a zero written as +0; idx = 2 dh + dw of the winner, or
+ *     4 where t_winner <= 0 (a dead window).
+ * Backward (needs neither x nor y):
+ *     gz[h][w][n] takes the bits of g[h/2][w/2][n] where idx[h/2][w/2][n] == 2 (h & 1) + (w & 1), else +0; it is formed
+ *     while g is staged in LDS and never written to memory.
+ *     gx[c][h][w] = round( inv_std[c] * sum_{kh,kw,n} gz[h+1-kh][w+1-kw][n] * w[n][c][kh][kw] ): per accumulator the taps in
+ *     the order kh*3+kw, within a tap channels 0..31 in one MFMA before 32..63 in the next; the product with inv_std is
+ *     one fp32 operation, then the rounding to the storage type.
+ * Limits: H, W even and >= 2, 1 <= B <= 65535 (the image index is a grid dimension), B * H * W < 2^31, dtype ADIL_F32 or
+ * ADIL_BF16, non-null pointers aligned to 16 bytes (x, gx: their element size; idx of the backward: 8); anything else
+ * ADIL_EINVAL before any launch, outputs untouched.  Out-of-range positions are never loaded (predicated), so nothing of
+ * a neighbouring image is read and a NaN in one image never reaches another.  One launch each on `stream`, no allocation,
+ * no synchronisation, no atomics (bitwise reproducible), capturable, 64-bit element offsets; every element of y, idx and
+ * gx is written, nothing behind them. */
+int adil_first3x3_pool_fwd(const void* x, int x_dtype, const void* w_fwd, float mean0, float mean1, float mean2,
+                           float inv_std0, float inv_std1, float inv_std2, const float* bias, void* y, void* idx, int B,
+                           int H, int W, void* stream);
+int adil_first3x3_pool_bwd(const void* g, const void* idx, const void* w_bwd, float inv_std0, float inv_std1,
+                           float inv_std2, void* gx, int gx_dtype, int B, int H, int W, void* stream);
 
 #ifdef __cplusplus
 }
