@@ -7,7 +7,8 @@
 //                               tile, and every tile gives the same bits)
 //   pw_join                     conv3 of a bottleneck and conv1 of the next one as one kernel, forward and input
 //                               gradient (the C-channel tensor between them stays on chip)
-//   conv3x3                    3x3 / stride-1 convolutions as an implicit GEMM with linear pixel tiling
+//   conv3x3_s2                  3x3 / stride-2 convolutions as tap-GEMMs, forward and input gradient (the stride-1 ones:
+//                               adil_conv3x3.hip)
 // Not part of the ADiL maths: the parity target is plain PyTorch (tests/test_gpu_stem.py).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -983,263 +984,6 @@ extern "C" int adil_pw_join_bwd(const void* g_h1, const void* h1, const float* s
 }
 
 // =========================================================================================================== //
-// 3x3 / stride 1 / pad 1 convolution of the frozen ResNet (conv2 of every bottleneck), NHWC bf16, raw output:
-// its BatchNorm + ReLU live in the next pointwise kernel's prologue, so this kernel is a pure implicit GEMM
-//     Y[m][n] = sum_{tap, c} X[m + (kh-1)*W + (kw-1)][c] * Wp[n][tap][c]        (taps crossing an image edge masked)
-// and the input gradient is the same kernel on flipped / transposed weights.  Pixels are tiled LINEARLY (128
-// consecutive (n,h,w) indices, any H, W): the halo of a tile is the contiguous range [m0-W-1, m0+128+W+1), staged
-// once per 64-channel chunk; the fragment of a lane's pixel for tap (kh,kw) is the LDS row pl + kh*W + kw.
-// Per tap one weight tile (double buffered, next tile's global loads in flight), ONE barrier, 16 MFMAs per wave on
-// 64 px x 64 (32) channel wave tiles.  No zero-fill launch, no epilogue pass.
-// =========================================================================================================== //
-namespace {
-
-#define C3_LS 72
-
-// The main loop: a run-time loop over 64-channel chunks with the 9 taps unrolled (constant kh, kw, mask bit; one 32-bit
-// weight offset per thread plus a scalar), two fragment register sets so that the LDS reads of ks + 1 fly under the MFMAs
-// of ks, and the barrier between the MFMAs of ks = 2 and ks = 3: the first fragments of the next tap are read under
-// ks = 3.  A masked tap reads a row of zeros instead of selecting on the fragments (the centre tap needs neither).  Per
-// accumulator the MFMAs run chunk -> tap -> ks (tests/golden/retired_variant_bits.json holds the bits of that order).
-template <int BN, int WPX>                              // WPX waves along pixels (64 each) x 4/WPX along channels
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2))) void conv3x3_kernel(
-    const bf16_t* __restrict__ x, const bf16_t* __restrict__ wp, bf16_t* __restrict__ y, int M, int H, int W, int C, int N,
-    int MT, int NT) {
-    constexpr int C3_BM = WPX * 64;                      // pixels per workgroup: 128 (2 x 2 waves) or 256 (4 x 1 waves)
-    constexpr int CTW = BN / 32 / (4 / WPX);             // channel tiles per wave
-    constexpr int XCHK = (C3_BM + 128) * 8 / 256;        // halo chunks per thread (NP <= C3_BM + 128: W <= 63)
-    constexpr int WCH = BN * 8 / 256;                    // 16-byte chunks of a weight tile per thread
-    constexpr int OS = BN + 8;
-    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
-    const int NP = C3_BM + 2 * W + 2;                    // halo pixels
-    bf16_t* sx = reinterpret_cast<bf16_t*>(smem_raw);    // [NP][C3_LS]  (later: [128][OS] output transpose)
-    const int sx_elems = (NP * C3_LS > C3_BM * OS ? NP * C3_LS : C3_BM * OS);
-    bf16_t* sw = sx + ((sx_elems + 7) & ~7);             // [2][BN][C3_LS]
-    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, c = lane & 31, h = lane >> 5;
-    const int wpx = w % WPX, wch = w / WPX;
-    int mt, nt;
-    if ((MT & 7) == 0) {
-        const int xcd = blockIdx.x & 7, j = blockIdx.x >> 3;
-        nt = j % NT;
-        mt = (j / NT) * 8 + xcd;
-    } else {
-        nt = blockIdx.x % NT;
-        mt = blockIdx.x / NT;
-    }
-    const int m0 = mt * C3_BM, n0 = nt * BN;
-    const int nci = C >> 6;
-
-    // this lane's two pixels and the validity of their 9 taps
-    int pl[2];
-    unsigned vmask[2];
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-        pl[p] = (wpx * 2 + p) * 32 + c;
-        const int m = m0 + pl[p];
-        const int ww = m % W, hh = (m / W) % H;
-        unsigned vm = 0;
-#pragma unroll
-        for (int t = 0; t < 9; ++t) {
-            const int kh = t / 3, kw = t - 3 * kh;
-            const bool ok = (m < M) && (hh + kh - 1 >= 0) && (hh + kh - 1 < H) && (ww + kw - 1 >= 0) && (ww + kw - 1 < W);
-            vm |= ok ? (1u << t) : 0u;
-        }
-        vmask[p] = vm;
-    }
-
-    u32x4 xr[XCHK], wr[3][WCH];                           // weight tiles are requested THREE taps ahead (an L2 round trip
-                                                          // is ~5x the 16 MFMAs of one tap)
-    auto store_x = [&]() {
-#pragma unroll
-        for (int i = 0; i < XCHK; ++i) {
-            const int q = tid + 256 * i, px = q >> 3, ch = q & 7;
-            if (px < NP) *reinterpret_cast<u32x4*>(sx + px * C3_LS + ch * 8) = xr[i];
-        }
-    };
-    auto store_w = [&](int buf, const u32x4 (&r)[WCH]) {
-#pragma unroll
-        for (int i = 0; i < WCH; ++i) {
-            const int q = tid + 256 * i, row = q >> 3, ch = q & 7;
-            *reinterpret_cast<u32x4*>(sw + (buf * BN + row) * C3_LS + ch * 8) = r[i];
-        }
-    };
-
-    f32x16 acc[2][CTW];
-#pragma unroll
-    for (int p = 0; p < 2; ++p)
-#pragma unroll
-        for (int ct = 0; ct < CTW; ++ct)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) acc[p][ct][r] = 0.0f;
-
-    // ---- addresses, once.  Weights: one 32-bit byte offset per thread (the launcher refuses packs of 2^31 elements
-    // or more) on a uniform base that advances by C per tap and 64 per chunk.  Halo: 32-bit byte offsets from the
-    // tile's first halo row (at most C3_BM + 128 rows of C elements: far below 2^32 bytes wherever the pack fits).
-    const unsigned wq = (((unsigned)(n0 + (tid >> 3)) * 9u) * (unsigned)C + (unsigned)(tid & 7) * 8u) * 2u;
-    const size_t wrow = (size_t)32 * 9 * C;                       // elements between a thread's weight rows (uniform)
-    auto load_w = [&](unsigned ws, u32x4 (&r)[WCH]) {            // ws = tap * C + cc * 64
-#pragma unroll
-        for (int i = 0; i < WCH; ++i)
-            r[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(wp + ws + i * wrow) + wq);
-    };
-    const int gmb = m0 - W - 1 > 0 ? m0 - W - 1 : 0;
-    const bf16_t* xb = x + (size_t)gmb * C;
-    unsigned xq[XCHK];
-#pragma unroll
-    for (int i = 0; i < XCHK; ++i) {
-        const int px = (tid >> 3) + 32 * i;
-        int gm = m0 - W - 1 + (px < NP ? px : NP - 1);
-        gm = gm < 0 ? 0 : (gm >= M ? M - 1 : gm);
-        xq[i] = ((unsigned)(gm - gmb) * (unsigned)C + (unsigned)(tid & 7) * 8u) * 2u;
-    }
-    auto load_x = [&](int cc) {
-#pragma unroll
-        for (int i = 0; i < XCHK; ++i)
-            xr[i] = *reinterpret_cast<const u32x4*>(reinterpret_cast<const char*>(xb + cc * 64) + xq[i]);
-    };
-    bf16_t* sz = sw + 2 * BN * C3_LS;                             // [C3_LS] zeros: what a tap outside the image reads
-    const bf16_t* xl0 = sx + pl[0] * C3_LS + 8 * h;
-    const bf16_t* xl1 = sx + pl[1] * C3_LS + 8 * h;
-    const bf16_t* zl = sz + 8 * h;
-    const bf16_t* bwl = sw + ((wch * CTW) * 32 + c) * C3_LS + 8 * h;
-    // the LDS row of pixel p's fragment at a tap (a constant after unrolling); a lane past M computes a row that
-    // is never written, so the centre tap, which never leaves the image, takes no select
-    auto xrow = [&](const bf16_t* xl, unsigned vm, int tap) -> const bf16_t* {
-        const int kh = tap / 3, kw = tap - 3 * kh;
-        const bf16_t* a = xl + (kh * W + kw) * C3_LS;
-        if (tap == 4) return a;
-        return (vm & (1u << tap)) ? a : zl;
-    };
-    struct Frag {
-        bf16x8 b0, b1, a[CTW];
-    };
-    auto read_frag = [&](Frag& f, const bf16_t* p0, const bf16_t* p1, const bf16_t* bw, int ks) {
-        f.b0 = lds8(p0 + 16 * ks);
-        f.b1 = lds8(p1 + 16 * ks);
-#pragma unroll
-        for (int ct = 0; ct < CTW; ++ct) f.a[ct] = lds8(bw + ct * 32 * C3_LS + 16 * ks);
-    };
-    auto mma_frag = [&](const Frag& f) {
-#pragma unroll
-        for (int ct = 0; ct < CTW; ++ct) {
-            mma16(acc[0][ct], f.a[ct], f.b0);
-            mma16(acc[1][ct], f.a[ct], f.b1);
-        }
-    };
-
-    load_x(0);
-    load_w(0u, wr[0]);
-    load_w((unsigned)C, wr[1]);
-    load_w(2u * (unsigned)C, wr[2]);
-    store_x();
-    store_w(0, wr[0]);
-    if (tid < C3_LS / 8) reinterpret_cast<u32x4*>(sz)[tid] = u32x4{0u, 0u, 0u, 0u};
-    __syncthreads();
-    Frag fa, fb;                                                  // fa: ks 0 and 2, fb: ks 1 and 3
-    const bf16_t* p0 = xrow(xl0, vmask[0], 0);
-    const bf16_t* p1 = xrow(xl1, vmask[1], 0);
-    read_frag(fa, p0, p1, bwl, 0);
-    for (int cc = 0; cc < nci; ++cc) {
-        const bool more = cc + 1 < nci;
-        const unsigned wsc = (unsigned)cc * 64u, wsn = (unsigned)(more ? cc + 1 : cc) * 64u;   // surplus loads: clamped, never stored
-#pragma unroll
-        for (int tap = 0; tap < 9; ++tap) {                       // 9 = 3 x 3: the register-set rotation closes per chunk
-            // on entry: sw[buf] holds this tap's tile and fa its ks = 0 fragments (in flight); wr[(tap+1) % 3] holds
-            // the next tile, wr[(tap+2) % 3] the one after it (in flight), wr[tap % 3]'s tile is already in LDS
-            const int buf = (cc + tap) & 1;                       // tile cc * 9 + tap
-            const bf16_t* bw = bwl + buf * BN * C3_LS;
-            const bool last = !more && tap == 8;
-            read_frag(fb, p0, p1, bw, 1);
-            if (!last) store_w(buf ^ 1, wr[(tap + 1) % 3]);       // read last before the previous barrier
-            load_w(tap + 3 < 9 ? wsc + (unsigned)((tap + 3) * C) : wsn + (unsigned)((tap - 6) * C), wr[tap % 3]);
-            if (tap == 4 && more) load_x(cc + 1);                // next channel chunk's halo flies under taps 4..8
-            __builtin_amdgcn_sched_barrier(0);
-            mma_frag(fa);
-            __builtin_amdgcn_sched_barrier(0);
-            read_frag(fa, p0, p1, bw, 2);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_frag(fb);
-            __builtin_amdgcn_sched_barrier(0);
-            read_frag(fb, p0, p1, bw, 3);
-            __builtin_amdgcn_sched_barrier(0);
-            mma_frag(fa);
-            __builtin_amdgcn_sched_barrier(0);
-            // every wave has read all of this tap's fragments and written the next tile: the barrier sits under
-            // the MFMAs of ks = 3, and so do the first reads of the next tap
-            lds_barrier();
-            if (tap == 8 && more) {                               // all waves are done with this halo
-                store_x();
-                lds_barrier();
-            }
-            if (!last) {
-                p0 = xrow(xl0, vmask[0], (tap + 1) % 9);
-                p1 = xrow(xl1, vmask[1], (tap + 1) % 9);
-                read_frag(fa, p0, p1, bwl + (buf ^ 1) * BN * C3_LS, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-            mma_frag(fb);
-            __builtin_amdgcn_sched_barrier(0);
-        }
-    }
-    // epilogue: transpose through LDS (all waves share one [128][OS] tile), 16-byte NHWC stores
-#pragma unroll
-    for (int p = 0; p < 2; ++p) {
-#pragma unroll
-        for (int ct = 0; ct < CTW; ++ct) {
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                u32x2 t;
-                t[0] = pack2_bf16(acc[p][ct][4 * q], acc[p][ct][4 * q + 1]);
-                t[1] = pack2_bf16(acc[p][ct][4 * q + 2], acc[p][ct][4 * q + 3]);
-                *reinterpret_cast<u32x2*>(sx + pl[p] * OS + (wch * CTW + ct) * 32 + 8 * q + 4 * h) = t;
-            }
-        }
-    }
-    __syncthreads();
-    constexpr int CPP = BN / 8;
-#pragma unroll
-    for (int i = 0; i < C3_BM * CPP / 256; ++i) {
-        const int id = tid + 256 * i, px = id / CPP, ch = id - px * CPP;
-        const int mm = m0 + px;
-        if (mm < M) *reinterpret_cast<u32x4*>(y + (size_t)mm * N + n0 + ch * 8) = *reinterpret_cast<const u32x4*>(sx + px * OS + ch * 8);
-    }
-}
-
-template <int BN, int WPX>
-int launch_conv3x3(const void* x, const void* wp, void* y, int M, int H, int W, int C, int N, hipStream_t st) {
-    constexpr int C3_BM = WPX * 64;
-    const int MT = (M + C3_BM - 1) / C3_BM, NT = N / BN;
-    const int NP = C3_BM + 2 * W + 2;
-    size_t sx_elems = (size_t)NP * C3_LS;
-    if (sx_elems < (size_t)C3_BM * (BN + 8)) sx_elems = (size_t)C3_BM * (BN + 8);
-    sx_elems = (sx_elems + 7) & ~(size_t)7;
-    const size_t lds = (sx_elems + (size_t)2 * BN * C3_LS + C3_LS) * sizeof(bf16_t);   // halo | two weight tiles | the row of zeros
-    if (lds > 160 * 1024) return ADIL_EINVAL;
-    if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)conv3x3_kernel<BN, WPX>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (e != hipSuccess) return (int)e;
-    }
-    hipLaunchKernelGGL((conv3x3_kernel<BN, WPX>), dim3((unsigned)(MT * NT)), dim3(256), lds, st, (const bf16_t*)x,
-                       (const bf16_t*)wp, (bf16_t*)y, M, H, W, C, N, MT, NT);
-    ADIL_CHECK_LAUNCH();
-    return 0;
-}
-
-}  // namespace
-
-extern "C" int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H, int W, int C, int N, void* stream) {
-    ADIL_ENTER();
-    if (!x || !wp || !y || B <= 0 || H <= 0 || W <= 0 || C <= 0 || N <= 0 || (C % 64) || (N % 64) || W > 63) return ADIL_EINVAL;   // halo = 128 + 2W + 2 pixels <= 256
-    const long long M = (long long)B * H * W;
-    if (M > 0x7fffffffLL) return ADIL_EINVAL;
-    if (9LL * C * N > 0x7fffffffLL) return ADIL_EINVAL;               // weight offsets are 32-bit element indices
-    const hipStream_t st = (hipStream_t)stream;
-    if (N % 128 == 0) return launch_conv3x3<128, 2>(x, wp, y, (int)M, H, W, C, N, st);
-    return launch_conv3x3<64, 4>(x, wp, y, (int)M, H, W, C, N, st);   // 64 px x 64 ch wave tiles as well
-}
-
-// =========================================================================================================== //
 // 3x3 / stride 2 / pad 1 convolution of the frozen ResNet (conv2 of the first bottleneck of stages 2-4; conv1 of the
 // same BasicBlocks), NHWC bf16, raw output, forward AND input gradient, even H and W.  Both are a sum of tap-GEMMs
 // over rows r = (b, i, j) of the OH x OW = H/2 x W/2 grid:
@@ -1260,8 +1004,9 @@ extern "C" int adil_conv3x3(const void* x, const void* wp, void* y, int B, int H
 namespace {
 
 #define S2_BM 128
+#define C3_LS 72                       // LDS row pitch in bf16 (64 channels + 8), as in conv3x3_kernel
 
-// The main loop is conv3x3_kernel's as far as it has the same shape (the taps stay run-time values: the gradient's classes
+// The main loop is conv3x3_kernel's (adil_conv3x3.hip) as far as it has the same shape (the taps stay run-time values: the gradient's classes
 // have 4 / 2 / 2 / 1 of them): per-thread byte offsets computed once (weights 32-bit on a uniform base, source rows plus a
 // uniform tap offset); at BN = 64 two fragment register sets and the barrier between the MFMAs of ks = 2 and ks = 3, a
 // finished class then leaving through the buffer whose tile it has just multiplied; at BN = 128 the second fragment set

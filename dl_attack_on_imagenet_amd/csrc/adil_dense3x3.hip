@@ -2,7 +2,7 @@
 // behind every dense layer of the frozen DenseNet-121 — forward and input gradient: adil_dense3x3_fwd /
 // adil_dense3x3_bwd (include/adil_hip.h).  bf16 channels_last storage, raw output (no epilogue), bf16 MFMA with fp32
 // accumulation, one rounding to bf16 (RNE), no atomics, 64-bit element offsets.  A sibling of conv3x3_kernel
-// (adil_convs.hip), which needs 64 channels on both sides and stays as it is.
+// (adil_conv3x3.hip), which needs 64 channels on both sides and stays as it is.
 //
 // Both directions are the implicit GEMM
 //     OUT[m][o] = sum_{tap, r} SRC[m + (kh-1)*W + (kw-1)][r] * WP[o][tap][r]      (taps leaving the image are SELECTED away)

@@ -21,12 +21,11 @@
 #include <stdint.h>
 
 #include "adil_common.h"
+#include "adil_first_patch.h"
 #include "adil_hip.h"
 #include "adil_mfma.h"
 
 namespace {
-
-struct FirstNorm { float mean[3]; float inv_std[3]; };
 
 #define FC_T 16                        // conv-output tile edge
 #define FC_ROWS (2 * FC_T + 1)         // 33 input rows
@@ -37,7 +36,7 @@ struct FirstNorm { float mean[3]; float inv_std[3]; };
 
 template <typename TX, bool RELU6>
 __global__ __launch_bounds__(256) void first3x3_fwd_kernel(const TX* __restrict__ x, const bf16_t* __restrict__ wf,
-                                                           FirstNorm nm, const float* __restrict__ scale,
+                                                           InputNorm nm, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, bf16_t* __restrict__ y,
                                                            int H, int W, int OH, int OW) {
     __shared__ __attribute__((aligned(16))) bf16_t sin[FC_ROWS * FC_RS];
@@ -168,7 +167,7 @@ __device__ __forceinline__ void first_bwd_class(f32x4 (&acc)[2], const bf16_t* s
 template <typename TX, bool RELU6>
 __global__ __launch_bounds__(256) void first3x3_bwd_kernel(const bf16_t* __restrict__ g, const bf16_t* __restrict__ y,
                                                            const float* __restrict__ scale, const bf16_t* __restrict__ wb,
-                                                           FirstNorm nm, TX* __restrict__ gx, int H, int W, int OH,
+                                                           InputNorm nm, TX* __restrict__ gx, int H, int W, int OH,
                                                            int OW) {
     __shared__ __attribute__((aligned(16))) bf16_t sg[FB_GR * FB_GC * FB_PS];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -263,7 +262,7 @@ extern "C" int adil_first3x3_fwd(const void* x, int x_dtype, const void* w_fwd, 
         !aligned(shift, 4))
         return ADIL_EINVAL;
     ADIL_ENTER();
-    const FirstNorm nm = {{mean0, mean1, mean2}, {inv_std0, inv_std1, inv_std2}};
+    const InputNorm nm = {{mean0, mean1, mean2}, {inv_std0, inv_std1, inv_std2}};
     const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
     const dim3 grid((OW + FC_T - 1) / FC_T, (OH + FC_T - 1) / FC_T, B), block(256);
     if (grid.y > 65535u) return ADIL_EINVAL;
@@ -289,7 +288,7 @@ extern "C" int adil_first3x3_bwd(const void* g, const void* y, const float* scal
         !aligned(gx, gx_dtype == ADIL_F32 ? 4 : 2))
         return ADIL_EINVAL;
     ADIL_ENTER();
-    const FirstNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};
+    const InputNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};
     const int OH = (H - 1) / 2 + 1, OW = (W - 1) / 2 + 1;
     const dim3 grid((W + FB_TW - 1) / FB_TW, (H + FB_TH - 1) / FB_TH, B), block(256);
     if (grid.y > 65535u) return ADIL_EINVAL;

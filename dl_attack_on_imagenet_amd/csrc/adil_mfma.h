@@ -1,5 +1,5 @@
 // adil_mfma.h — small device helpers shared by the frozen-classifier kernels (adil_stem.hip, adil_convs.hip,
-// adil_pointwise8.hip, adil_first_conv.hip, adil_dense1x1.hip, adil_dense3x3.hip, adil_dense_transition.hip, and
+// adil_conv3x3.hip, adil_bias_relu_pool2.hip, adil_pointwise8.hip, adil_first_conv.hip, adil_vgg_first.hip, adil_dense1x1.hip, adil_dense3x3.hip, adil_dense_transition.hip, and
 // adil_pw_tile.h, the tile the narrow pointwise kernels share).
 #pragma once
 #include <hip/hip_runtime.h>

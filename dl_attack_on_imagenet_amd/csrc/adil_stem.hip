@@ -15,12 +15,11 @@
 #include <stdint.h>
 
 #include "adil_common.h"
+#include "adil_first_patch.h"                          // InputNorm
 #include "adil_hip.h"
 #include "adil_mfma.h"
 
 namespace {
-
-struct StemNorm { float mean[3]; float inv_std[3]; };
 
 // =========================================================================================================== //
 // stem_conv_fwd.  Workgroup (4 waves) = a 16 x 16 tile of conv outputs of one image, all 64 channels.
@@ -40,7 +39,7 @@ struct StemNorm { float mean[3]; float inv_std[3]; };
 
 template <typename TX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void stem_conv_fwd_kernel(const TX* __restrict__ x, const bf16_t* __restrict__ wf,
-                                                            StemNorm nm, const float* __restrict__ scale,
+                                                            InputNorm nm, const float* __restrict__ scale,
                                                             const float* __restrict__ shift, bf16_t* __restrict__ y,
                                                             int H, int W, int OH, int OW) {
     // one LDS block: [input tile | weights]; the per-wave output-transpose scratch aliases it once the MFMAs are done
@@ -315,8 +314,8 @@ __global__ __launch_bounds__(256) void stem_pool_bwd_quad_kernel(const bf16_t* _
 #define SQ_WN (2 * SQ_WCI + 6 * SQ_WKH + 7 * 64)   // weight image, followed by one zero chunk
 
 // v_mfma_f32_16x16x32_bf16: A lane l -> row l&15, k = 8*(l>>4)+j; B lane l -> column l&15, same k; C register r of
-// lane l -> row 4*(l>>4)+r, column l&15 (layout checked on hardware): 16 pixels x 32 channels of K per instruction.
-typedef float f32x4 __attribute__((ext_vector_type(4)));
+// lane l -> row 4*(l>>4)+r, column l&15 (layout checked on hardware): 16 pixels x 32 channels of K per instruction
+// (f32x4: adil_first_patch.h).
 
 template <typename TX> __device__ __forceinline__ void st_pair(TX* p, float a, float b);
 template <> __device__ __forceinline__ void st_pair<float>(float* p, float a, float b) {
@@ -328,7 +327,7 @@ template <> __device__ __forceinline__ void st_pair<bf16_t>(bf16_t* p, float a, 
 
 template <typename TX>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void stem_conv_bwd_shift_kernel(
-    const bf16_t* __restrict__ gy, const bf16_t* __restrict__ wb, StemNorm nm, TX* __restrict__ gx, int H, int W, int OH,
+    const bf16_t* __restrict__ gy, const bf16_t* __restrict__ wb, InputNorm nm, TX* __restrict__ gx, int H, int W, int OH,
     int OW, int NTX, int NTY, int ntiles) {
     __shared__ __attribute__((aligned(16))) bf16_t sg[SB_GR * SB_GC * SQ_PS];
     __shared__ __attribute__((aligned(16))) bf16_t swb[SQ_WN + 8];
@@ -454,7 +453,7 @@ extern "C" int adil_stem_conv_fwd(const void* x, int x_dtype, const void* w_fwd,
     // B is blockIdx.z: beyond 65535 images the outcome would be the runtime's (a launch error code, or a launch), so refuse
     if (!x || !w_fwd || !scale || !shift || !y || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return ADIL_EINVAL;
     if (x_dtype != ADIL_F32 && x_dtype != ADIL_BF16) return ADIL_EINVAL;
-    const StemNorm nm = {{mean0, mean1, mean2}, {inv_std0, inv_std1, inv_std2}};
+    const InputNorm nm = {{mean0, mean1, mean2}, {inv_std0, inv_std1, inv_std2}};
     const int OH = H / 2, OW = W / 2;
     const dim3 grid((OW + ST_T - 1) / ST_T, (OH + ST_T - 1) / ST_T, B);
     hipStream_t st = (hipStream_t)stream;
@@ -498,7 +497,7 @@ extern "C" int adil_stem_conv_bwd(const void* gy, const void* w_bwd, float inv_s
     ADIL_ENTER();
     if (!gy || !w_bwd || !gx || B <= 0 || B > 65535 || H <= 0 || W <= 0 || (H & 1) || (W & 1)) return ADIL_EINVAL;   // as the forward
     if (gx_dtype != ADIL_F32 && gx_dtype != ADIL_BF16) return ADIL_EINVAL;
-    const StemNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};
+    const InputNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};
     const int OH = H / 2, OW = W / 2;
     const int NTX = (W + SB_TW - 1) / SB_TW, NTY = (H + SB_TH - 1) / SB_TH;
     const long long ntiles = (long long)NTX * NTY * B;

@@ -29,12 +29,11 @@
 #include <stdint.h>
 
 #include "adil_common.h"
+#include "adil_first_patch.h"
 #include "adil_hip.h"
 #include "adil_mfma.h"
 
 namespace {
-
-struct VggNorm { float mean[3]; float inv_std[3]; };
 
 #define VF_TH 16                       // input rows of a forward tile
 #define VF_TW 32                       // input columns
@@ -45,7 +44,7 @@ struct VggNorm { float mean[3]; float inv_std[3]; };
 
 template <typename TX>
 __global__ __launch_bounds__(256, 3) void first3x3_pool_fwd_kernel(const TX* __restrict__ x, const bf16_t* __restrict__ wf,
-                                                                   VggNorm nm, const float* __restrict__ bias,
+                                                                   InputNorm nm, const float* __restrict__ bias,
                                                                    bf16_t* __restrict__ y, unsigned char* __restrict__ idx,
                                                                    int H, int W) {
     __shared__ __attribute__((aligned(16))) bf16_t sin[VF_ROWS * VF_RS];
@@ -185,7 +184,7 @@ __device__ __forceinline__ int vb_at(int row, int col, int q) { return ((row * V
 template <typename TX>
 __global__ __launch_bounds__(256, 2) void first3x3_pool_bwd_kernel(const bf16_t* __restrict__ g,
                                                                    const unsigned char* __restrict__ idx,
-                                                                   const bf16_t* __restrict__ wb, VggNorm nm,
+                                                                   const bf16_t* __restrict__ wb, InputNorm nm,
                                                                    TX* __restrict__ gx, int H, int W) {
     __shared__ __attribute__((aligned(16))) bf16_t sg[VB_HR * VB_HC * 64];
     const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
@@ -302,7 +301,7 @@ extern "C" int adil_first3x3_pool_fwd(const void* x, int x_dtype, const void* w_
         !aligned(idx, 16))
         return ADIL_EINVAL;
     ADIL_ENTER();
-    const VggNorm nm = {{mean0, mean1, mean2}, {inv_std0, inv_std1, inv_std2}};
+    const InputNorm nm = {{mean0, mean1, mean2}, {inv_std0, inv_std1, inv_std2}};
     const dim3 grid((W + VF_TW - 1) / VF_TW, (H + VF_TH - 1) / VF_TH, B), block(256);
     hipStream_t st = (hipStream_t)stream;
     const bf16_t* wp = (const bf16_t*)w_fwd;
@@ -322,7 +321,7 @@ extern "C" int adil_first3x3_pool_bwd(const void* g, const void* idx, const void
     if (!aligned(g, 16) || !aligned(idx, 8) || !aligned(w_bwd, 16) || !aligned(gx, gx_dtype == ADIL_F32 ? 4 : 2))
         return ADIL_EINVAL;
     ADIL_ENTER();
-    const VggNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};
+    const InputNorm nm = {{0.0f, 0.0f, 0.0f}, {inv_std0, inv_std1, inv_std2}};
     const dim3 grid((W + VB_TW - 1) / VB_TW, (H + VB_TH - 1) / VB_TH, B), block(256);
     hipStream_t st = (hipStream_t)stream;
     const bf16_t* gp = (const bf16_t*)g;

@@ -920,37 +920,38 @@ def pack_conv3x3_weights(weight: Tensor) -> Tuple[Tensor, Tensor]:
 
 
 class Conv3x3Function(torch.autograd.Function):
-    """3x3 / stride 1 / pad 1 convolution on channels_last bf16 tensors (adil_conv3x3), raw output; the input gradient
-    is the same kernel on the flipped / transposed weights.  No weight gradient: the network is frozen."""
+    """3x3 / stride 1 / pad 1 convolution on channels_last bf16 tensors, raw output, through `entry`: adil_conv3x3 (linear
+    pixel tiles, W <= 63) or adil_conv3x3_wide (2-D tiles, any width), the same convolution, packs and bits.  The input
+    gradient is the same kernel on the flipped / transposed weights.  No weight gradient: the network is frozen."""
 
     @staticmethod
-    def forward(ctx, x, wp_fwd, wp_bwd):
+    def forward(ctx, x, wp_fwd, wp_bwd, entry="adil_conv3x3"):
         lib = _lib.load()
         b, c, h, w = x.shape
         n = wp_fwd.shape[0]
         x2 = _nhwc(x)
         y = torch.empty((b, h, w, n), dtype=torch.bfloat16, device=x.device)
         if b > 0:
-            _lib.check(lib.adil_conv3x3(_ptr(x2), _ptr(wp_fwd), _ptr(y), b, h, w, c, n, _stream()), "adil_conv3x3")
+            _lib.check(getattr(lib, entry)(_ptr(x2), _ptr(wp_fwd), _ptr(y), b, h, w, c, n, _stream()), entry)
         ctx.save_for_backward(wp_bwd)
-        ctx.meta = (c,)
+        ctx.meta = (c, entry)
         return y.permute(0, 3, 1, 2)
 
     @staticmethod
     def backward(ctx, g):
         lib = _lib.load()
         (wp_bwd,) = ctx.saved_tensors
-        (c,) = ctx.meta
+        c, entry = ctx.meta
         g2 = _nhwc_grad(g)
         b, h, w, n = g2.shape
         gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
         if b > 0:
-            _lib.check(lib.adil_conv3x3(_ptr(g2), _ptr(wp_bwd), _ptr(gx), b, h, w, n, c, _stream()), "adil_conv3x3")
-        return gx.permute(0, 3, 1, 2), None, None
+            _lib.check(getattr(lib, entry)(_ptr(g2), _ptr(wp_bwd), _ptr(gx), b, h, w, n, c, _stream()), entry)
+        return gx.permute(0, 3, 1, 2), None, None, None
 
 
 def conv3x3(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
-    return Conv3x3Function.apply(x, wp_fwd, wp_bwd)
+    return Conv3x3Function.apply(x, wp_fwd, wp_bwd, "adil_conv3x3")
 
 
 def conv3x3_wide_covers(x: Tensor, cin: int, cout: int) -> bool:
@@ -958,36 +959,6 @@ def conv3x3_wide_covers(x: Tensor, cin: int, cout: int) -> bool:
     return (x.dim() == 4 and x.is_cuda and x.dtype == torch.bfloat16 and x.shape[1] == cin and cin > 0 and cout > 0
             and cin % 64 == 0 and cout % 64 == 0 and min(x.shape[0], x.shape[2], x.shape[3]) > 0
             and x.shape[0] * x.shape[2] * x.shape[3] < 2 ** 31 and 9 * cin * cout < 2 ** 31)
-
-
-class Conv3x3WideFunction(torch.autograd.Function):
-    """`Conv3x3Function` on adil_conv3x3_wide: the same convolution, packs and bits on 2-D pixel tiles, for any width.
-    No weight gradient: the network is frozen."""
-
-    @staticmethod
-    def forward(ctx, x, wp_fwd, wp_bwd):
-        lib = _lib.load()
-        b, c, h, w = x.shape
-        n = wp_fwd.shape[0]
-        x2 = _nhwc(x)
-        y = torch.empty((b, h, w, n), dtype=torch.bfloat16, device=x.device)
-        if b > 0:
-            _lib.check(lib.adil_conv3x3_wide(_ptr(x2), _ptr(wp_fwd), _ptr(y), b, h, w, c, n, _stream()), "adil_conv3x3_wide")
-        ctx.save_for_backward(wp_bwd)
-        ctx.meta = (c,)
-        return y.permute(0, 3, 1, 2)
-
-    @staticmethod
-    def backward(ctx, g):
-        lib = _lib.load()
-        (wp_bwd,) = ctx.saved_tensors
-        (c,) = ctx.meta
-        g2 = _nhwc_grad(g)
-        b, h, w, n = g2.shape
-        gx = torch.empty((b, h, w, c), dtype=torch.bfloat16, device=g2.device)
-        if b > 0:
-            _lib.check(lib.adil_conv3x3_wide(_ptr(g2), _ptr(wp_bwd), _ptr(gx), b, h, w, n, c, _stream()), "adil_conv3x3_wide")
-        return gx.permute(0, 3, 1, 2), None, None
 
 
 def conv3x3_wide(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
@@ -1006,7 +977,7 @@ def conv3x3_wide(x: Tensor, wp_fwd: Tensor, wp_bwd: Tensor) -> Tensor:
     if not x.permute(0, 2, 3, 1).is_contiguous():
         raise ValueError("x must be in channels_last memory format (the kernel reads it in place)")
     _check_operands(x.device, ("wp_fwd", wp_fwd, (n, 9 * c), torch.bfloat16), ("wp_bwd", wp_bwd, (c, 9 * n), torch.bfloat16))
-    return Conv3x3WideFunction.apply(x, wp_fwd, wp_bwd)
+    return Conv3x3Function.apply(x, wp_fwd, wp_bwd, "adil_conv3x3_wide")
 
 
 def bias_relu_pool2_covers(x: Tensor) -> bool:

@@ -1,4 +1,4 @@
-"""float64 restatements of the frozen-classifier kernels (csrc/adil_convs.hip, csrc/adil_stem.hip, affine_act in
+"""float64 restatements of the frozen-classifier kernels (csrc/adil_convs.hip, csrc/adil_conv3x3.hip, csrc/adil_stem.hip, affine_act in
 csrc/adil_update.hip), operand generators and two comparators.  Plain torch; works on the CPU and on a GPU.
 
 The kernels multiply bf16 operands, accumulate in fp32 and round ONCE to bf16, to nearest even.  Two legs use that:

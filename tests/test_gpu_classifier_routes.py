@@ -1,4 +1,4 @@
-"""Every launcher branch of the frozen-classifier kernels (csrc/adil_convs.hip, csrc/adil_stem.hip, affine_act) through
+"""Every launcher branch of the frozen-classifier kernels (csrc/adil_convs.hip, csrc/adil_conv3x3.hip, csrc/adil_stem.hip, affine_act) through
 the C ABI against the float64 restatements of tests/classifier_reference.py, on two legs per row:
 
 exact     integer operands, power-of-two scales: the kernel's bits must EQUAL the RNE bf16 rounding of the fp64 value

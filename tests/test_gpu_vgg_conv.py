@@ -1,4 +1,4 @@
-"""GPU: the VGG kernels (csrc/adil_conv3x3_wide.hip) through the C ABI — adil_conv3x3_wide against the fp64 restatement
+"""GPU: the VGG kernels (csrc/adil_conv3x3.hip, csrc/adil_bias_relu_pool2.hip) through the C ABI — adil_conv3x3_wide against the fp64 restatement
 of tests/classifier_reference.py (bit for bit on the exact leg, under the derived elementwise bound on the gaussian leg),
 adil_bias_relu_pool2_fwd / _bwd against torch's own fp32 chain and autograd on the CPU (bit for bit) — their autograd
 wrappers, and the VGG11 that runs seven of its eight convolutions and all its ReLUs and pools on them (`own_vgg_conv`)."""
@@ -79,9 +79,11 @@ def test_wide_conv_against_the_fp64_restatement(row):
     assert _same(_fwd(x, wp, row), y) and _same(_bwd(g, wp_bwd, row), gx)
 
 
-@pytest.mark.parametrize("row", [(3, 6, 10, 64, 64), (1, 9, 15, 512, 64), (1, 7, 15, 64, 128)], ids=str)
+@pytest.mark.parametrize("row", [(3, 6, 10, 64, 64), (1, 9, 15, 512, 64), (1, 7, 15, 64, 128), (2, 5, 9, 192, 128)], ids=str)
 def test_wide_conv_gives_the_bits_of_adil_conv3x3_where_both_cover(row):
-    """W <= 63: the linear-tile kernel and the 2-D-tile kernel run the same MFMAs per accumulator in the same order."""
+    """W <= 63: the linear-tile kernel and the 2-D-tile kernel run the same MFMAs per accumulator in the same order (one
+    kernel body, csrc/adil_conv3x3.hip).  The rows reach <64, 4> with one and with eight channel chunks and <128, 2> with
+    one and with three (the halo reload and the register rotation at a chunk boundary)."""
     r = vref.reference_row(row, "gaussian")
     B, H, W, C, N = row
     x, g, wp, wp_bwd = _dev(r.ops.x), _dev(r.ops.g), _dev(r.wp), _dev(r.wp_bwd)

@@ -1,4 +1,4 @@
-"""Row tables, operand generators and emulations of the VGG kernels (csrc/adil_conv3x3_wide.hip): the wide-image 3x3
+"""Row tables, operand generators and emulations of the VGG kernels (csrc/adil_conv3x3.hip, csrc/adil_bias_relu_pool2.hip): the wide-image 3x3
 convolution adil_conv3x3_wide and the bias + ReLU + 2x2 max-pool pair adil_bias_relu_pool2_fwd / _bwd.  The fp64
 restatement of the convolution, the two legs and the comparators are those of tests/classifier_reference.py (`conv3x3`,
 `conv3x3_bwd`, `compare_exact`, `assert_premise`, `gaussian_ratio`); nothing of them is restated here.
@@ -21,7 +21,7 @@ import torch.nn.functional as F
 from classifier_reference import (BF16, Arith, Gen, Out, assert_premise, compare_exact, conv3x3, conv3x3_bwd,  # noqa: F401
                                   finish, gaussian_ratio, pack_taps, pack_taps_flipped, rng, stats)
 
-TW = 16                          # tile width of conv3x3_wide_kernel
+TW = 16                          # tile width of conv3x3_kernel on 2-D tiles (adil_conv3x3_wide)
 
 
 def tile_rows(O):
